@@ -16,14 +16,51 @@ Launch:  python bench.py --gpus N --steps K --warmup W
 Rank 0 prints ONE JSON line with the whole-job metric (max epoch time over
 ranks) plus the comm-overlap statistics measured with HIP events on the side
 comm stream.
+
+A plain run does only what that line needs: set up, warm up, time K steps.
+`--dump-outputs DIR` additionally writes what the last timed step computed
+(logits, loss, updated parameters) as DIR/<name>.npy, so two builds can be
+compared output for output: with the same arguments the graph, features,
+initial weights and dropout streams are identical from run to run.
+`--full` is where measurements that need runs of their own belong; the
+benchmark has none today (overlap and peak-memory figures come out of the
+timed steps themselves), so it currently adds nothing to a plain run.
 """
 import argparse
 import json
 import os
 import time
 
+import numpy as np
 import torch
 import torch.distributed as dist
+
+DUMP_BUDGET_BYTES = 64 * 2**20
+
+
+def dump_outputs(out_dir, tensors, suffix=""):
+    """Write each tensor as out_dir/<name><suffix>.npy (float32, or float64
+    where the tensor is), at most DUMP_BUDGET_BYTES in all. When the
+    outputs exceed the budget every array gets a share proportional to its
+    size and keeps a fixed, evenly strided subset of its rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    tensors = {k: t.detach() for k, t in tensors.items()}
+
+    def nbytes(t):
+        return t.numel() * (8 if t.dtype == torch.float64 else 4)
+
+    total = sum(nbytes(t) for t in tensors.values())
+    for name, t in tensors.items():
+        if total > DUMP_BUDGET_BYTES and t.dim() > 0 and t.shape[0] > 1:
+            row_bytes = max(nbytes(t) // t.shape[0], 1)
+            share = DUMP_BUDGET_BYTES * nbytes(t) // total
+            k = max(min(share // row_bytes, t.shape[0]), 1)
+            idx = (torch.arange(k, dtype=torch.int64) * t.shape[0]) // k
+            t = t.index_select(0, idx.to(t.device))
+        if t.dtype != torch.float64:
+            t = t.float()
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"),
+                t.cpu().numpy())
 
 
 def main():
@@ -52,6 +89,14 @@ def main():
     ap.add_argument("--device", type=str, default=None)
     ap.add_argument("--backend", type=str, default=None,
                     help="override torch.distributed backend (tests)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one "
+                         "computed (logits, loss, updated parameters) as "
+                         "DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements that need runs of "
+                         "their own (none today: a plain run already "
+                         "yields every figure of the result line)")
     ap.add_argument("--solo-of", type=int, default=0,
                     help="sizing mode: run rank 0 of an N-way partition "
                          "alone on one GPU (full buffer layout + event "
@@ -59,6 +104,8 @@ def main():
                          "288 GB/GPU check: "
                          "`--shape ogbn-papers100m --solo-of 8`")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     if args.solo_of > 1:
         # sizing runs push toward the 288 GB HBM ceiling where caching-
@@ -291,6 +338,13 @@ def main():
                                 if device.startswith("cuda") else None),
             },
         }
+    if args.dump_outputs:
+        outs = {"logits": logits, "loss": loss}
+        for name, p in model.named_parameters():
+            outs["param." + name] = p
+        dump_outputs(args.dump_outputs, outs,
+                     suffix=f".rank{rank}" if world > 1 else "")
+    if rank == 0:
         print(json.dumps(result))
     dist.destroy_process_group()
 
