@@ -42,7 +42,7 @@ torch::Tensor spmm_cpu(torch::Tensor indptr, torch::Tensor indices,
                        torch::Tensor src_scale, int64_t num_rows);
 
 // ---------------------------------------------------------------------------
-// HIP kernel launchers (hip/kernels.hip) — gfx950 only.
+// HIP kernel launchers (hip/*.hip) — gfx950 only.
 // ---------------------------------------------------------------------------
 
 // out[r,:] = scale[r] * sum_{e in [indptr[r], indptr[r+1])} feat[indices[e],:]
@@ -55,9 +55,8 @@ void spmm_csr_hip(torch::Tensor indptr, torch::Tensor indices,
 // out[i,:] = src[idx[i],:]
 void gather_rows_hip(torch::Tensor src, torch::Tensor idx, torch::Tensor out);
 
-// dst[idx[i],:] += src[i,:]   (idx entries unique — no atomics needed? they
-// are unique for the boundary scatter; kernel uses one row per wave so
-// duplicates would race — documented contract: unique indices.)
+// dst[idx[i],:] += src[i,:]. Contract: idx entries are unique — one wave
+// owns each row and no atomics are used, so duplicates would race.
 void scatter_add_rows_hip(torch::Tensor dst, torch::Tensor idx,
                           torch::Tensor src);
 
@@ -80,7 +79,6 @@ void layer_norm_relu_fwd_hip(torch::Tensor x, torch::Tensor w,
                              torch::Tensor b, double eps, bool relu,
                              torch::Tensor y, torch::Tensor xhat,
                              torch::Tensor rstd);
-// dw_part/db_part: fp32 [nwaves, F] per-wave partials (column-sum on host).
 // fused dual data gradient: {g @ w1, g @ w2} via MFMA
 // (csrc/hip/dual_dgrad.hip)
 std::vector<torch::Tensor> dual_dgrad_hip(torch::Tensor g, torch::Tensor w1,
@@ -91,14 +89,16 @@ std::vector<torch::Tensor> dual_dgrad_hip(torch::Tensor g, torch::Tensor w1,
 std::vector<torch::Tensor> dual_wgrad_hip(torch::Tensor g, torch::Tensor x1,
                                           torch::Tensor x2);
 
+// dw_part/db_part: fp32 [nwaves, F] per-wave partials (column-sum on host).
 void layer_norm_relu_bwd_hip(torch::Tensor dy, torch::Tensor xhat,
                              torch::Tensor rstd, torch::Tensor w,
                              torch::Tensor b, bool relu, torch::Tensor dx,
                              torch::Tensor dw_part, torch::Tensor db_part);
 
-// Fused dual GEMM for the GraphSAGE layer epilogue:
-//   out[M,N] = x1[M,K] @ w1t[K,N] + x2[M,K] @ w2t[K,N] + b[N]
-// fp32, MFMA (v_mfma_f32_16x16x4_f32). Weights pre-transposed to [K,N].
-void sage_dual_gemm_hip(torch::Tensor x1, torch::Tensor x2, torch::Tensor w1t,
-                        torch::Tensor w2t, torch::Tensor bias,
+// Fused dual GEMM for the GraphSAGE layer forward:
+//   out[M,N] = x1[M,K] @ w1[N,K]^T + x2[M,K] @ w2[N,K]^T + bias[N]
+// fp32, MFMA (v_mfma_f32_32x32x2_f32). Weights in torch Linear layout [N,K],
+// not pre-transposed; an empty bias tensor means no bias.
+void sage_dual_gemm_hip(torch::Tensor x1, torch::Tensor x2, torch::Tensor w1,
+                        torch::Tensor w2, torch::Tensor bias,
                         torch::Tensor out);

@@ -18,13 +18,11 @@
 // VGPRs); the N reduction staged through LDS 32 rows at a time.
 
 #include "../common.h"
+#include "hip_util.h"
 
-#include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 #include <hip/hip_runtime.h>
 
 namespace {
-
-using f32x16 = __attribute__((__vector_size__(16 * sizeof(float)))) float;
 
 constexpr int DG_M = 128;  // output rows per block
 constexpr int DG_K = 64;   // output cols per block
@@ -107,16 +105,14 @@ __global__ __launch_bounds__(256) void dual_dgrad_kernel(
     __syncthreads();
   }
 
-  // epilogue: C layout for 32x32 shapes (same as dual_gemm.hip):
-  // col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
+  // epilogue: lane holds column l31 of each fragment, rows per mfma32_c_row
   const int64_t col = k0 + wc * 32 + l31;
   if (col >= K) return;
 #pragma unroll
   for (int fi = 0; fi < 2; ++fi)
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg) {
-      const int64_t row = m0 + wr * 64 + fi * 32 + (reg & 3) +
-                          8 * (reg >> 2) + 4 * lk;
+      const int64_t row = m0 + wr * 64 + fi * 32 + mfma32_c_row(reg, lk);
       if (row < M) {
         gx1[row * K + col] = acc1[fi][reg];
         gx2[row * K + col] = acc2[fi][reg];
@@ -139,12 +135,10 @@ std::vector<torch::Tensor> dual_dgrad_hip(torch::Tensor g, torch::Tensor w1,
   auto gx1 = torch::empty({M, K}, g.options());
   auto gx2 = torch::empty({M, K}, g.options());
   dim3 grid((M + DG_M - 1) / DG_M, (K + DG_K - 1) / DG_K);
-  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  hipLaunchKernelGGL(dual_dgrad_kernel, grid, dim3(256), 0, stream,
+  hipLaunchKernelGGL(dual_dgrad_kernel, grid, dim3(256), 0, current_stream(),
                      g.data_ptr<float>(), w1.data_ptr<float>(),
                      w2.data_ptr<float>(), gx1.data_ptr<float>(),
                      gx2.data_ptr<float>(), M, N, K);
-  hipError_t e = hipGetLastError();
-  TORCH_CHECK(e == hipSuccess, "HIP error: ", hipGetErrorString(e));
+  check_launch();
   return {gx1, gx2};
 }

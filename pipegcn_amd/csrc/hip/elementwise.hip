@@ -19,16 +19,10 @@
 // colsum_hip — the single-pass eager reduction was measured pathological).
 
 #include "../common.h"
+#include "hip_util.h"
 
-#include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 #include <hip/hip_bf16.h>
 #include <hip/hip_runtime.h>
-
-#define HIP_CHECK(expr)                                                  \
-  do {                                                                   \
-    hipError_t _e = (expr);                                              \
-    TORCH_CHECK(_e == hipSuccess, "HIP error: ", hipGetErrorString(_e)); \
-  } while (0)
 
 namespace {
 
@@ -336,10 +330,6 @@ __global__ void ln_bwd_kernel(const T* __restrict__ dy,
   }
 }
 
-inline hipStream_t cur_stream() {
-  return at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-}
-
 }  // namespace
 
 void dropout_fwd_hip(torch::Tensor x, torch::Tensor y, torch::Tensor mask,
@@ -359,18 +349,18 @@ void dropout_fwd_hip(torch::Tensor x, torch::Tensor y, torch::Tensor mask,
   TORCH_CHECK(bf16 || x.scalar_type() == torch::kFloat);
   if (bf16)
     hipLaunchKernelGGL(HIP_KERNEL_NAME(dropout_fwd_kernel<__hip_bfloat16>),
-                       dim3(blocks), dim3(threads), 0, cur_stream(),
+                       dim3(blocks), dim3(threads), 0, current_stream(),
                        reinterpret_cast<__hip_bfloat16*>(x.data_ptr()),
                        reinterpret_cast<__hip_bfloat16*>(y.data_ptr()),
                        mask.data_ptr<uint8_t>(), (uint64_t)seed, p16, scale,
                        n);
   else
     hipLaunchKernelGGL(HIP_KERNEL_NAME(dropout_fwd_kernel<float>),
-                       dim3(blocks), dim3(threads), 0, cur_stream(),
+                       dim3(blocks), dim3(threads), 0, current_stream(),
                        x.data_ptr<float>(), y.data_ptr<float>(),
                        mask.data_ptr<uint8_t>(), (uint64_t)seed, p16, scale,
                        n);
-  HIP_CHECK(hipGetLastError());
+  check_launch();
 }
 
 void dropout_bwd_hip(torch::Tensor dy, torch::Tensor mask, torch::Tensor dx,
@@ -386,17 +376,17 @@ void dropout_bwd_hip(torch::Tensor dy, torch::Tensor mask, torch::Tensor dx,
   const bool bf16 = dy.scalar_type() == torch::kBFloat16;
   if (bf16)
     hipLaunchKernelGGL(HIP_KERNEL_NAME(dropout_bwd_kernel<__hip_bfloat16>),
-                       dim3(blocks), dim3(threads), 0, cur_stream(),
+                       dim3(blocks), dim3(threads), 0, current_stream(),
                        reinterpret_cast<__hip_bfloat16*>(dy.data_ptr()),
                        mask.data_ptr<uint8_t>(),
                        reinterpret_cast<__hip_bfloat16*>(dx.data_ptr()),
                        scale, n);
   else
     hipLaunchKernelGGL(HIP_KERNEL_NAME(dropout_bwd_kernel<float>),
-                       dim3(blocks), dim3(threads), 0, cur_stream(),
+                       dim3(blocks), dim3(threads), 0, current_stream(),
                        dy.data_ptr<float>(), mask.data_ptr<uint8_t>(),
                        dx.data_ptr<float>(), scale, n);
-  HIP_CHECK(hipGetLastError());
+  check_launch();
 }
 
 void layer_norm_relu_fwd_hip(torch::Tensor x, torch::Tensor w,
@@ -417,7 +407,7 @@ void layer_norm_relu_fwd_hip(torch::Tensor x, torch::Tensor w,
   TORCH_CHECK(bf16 || x.scalar_type() == torch::kFloat);
   auto launch = [&](auto tptr, auto kernel) {
     using TP = decltype(tptr);
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, cur_stream(),
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, current_stream(),
                        reinterpret_cast<TP>(x.data_ptr()),
                        w.data_ptr<float>(), b.data_ptr<float>(),
                        reinterpret_cast<TP>(y.data_ptr()),
@@ -434,7 +424,7 @@ void layer_norm_relu_fwd_hip(torch::Tensor x, torch::Tensor w,
     launch((float*)nullptr, HIP_KERNEL_NAME(ln_fwd_kernel<float, true>));
   else
     launch((float*)nullptr, HIP_KERNEL_NAME(ln_fwd_kernel<float, false>));
-  HIP_CHECK(hipGetLastError());
+  check_launch();
 }
 
 void layer_norm_relu_bwd_hip(torch::Tensor dy, torch::Tensor xhat,
@@ -451,7 +441,7 @@ void layer_norm_relu_bwd_hip(torch::Tensor dy, torch::Tensor xhat,
   const bool bf16 = dy.scalar_type() == torch::kBFloat16;
   auto launch = [&](auto tptr, auto kernel) {
     using TP = decltype(tptr);
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, cur_stream(),
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, current_stream(),
                        reinterpret_cast<TP>(dy.data_ptr()),
                        reinterpret_cast<TP>(xhat.data_ptr()),
                        rstd.data_ptr<float>(), w.data_ptr<float>(),
@@ -470,5 +460,5 @@ void layer_norm_relu_bwd_hip(torch::Tensor dy, torch::Tensor xhat,
     launch((float*)nullptr, HIP_KERNEL_NAME(ln_bwd_kernel<float, true>));
   else
     launch((float*)nullptr, HIP_KERNEL_NAME(ln_bwd_kernel<float, false>));
-  HIP_CHECK(hipGetLastError());
+  check_launch();
 }

@@ -18,19 +18,13 @@
 //    halo graph, built once at setup — no atomics anywhere on the hot path.
 
 #include "../common.h"
+#include "hip_util.h"
 
-#include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 #include <hip/hip_bf16.h>
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
 #include <vector>
-
-#define HIP_CHECK(expr)                                              \
-  do {                                                               \
-    hipError_t _e = (expr);                                          \
-    TORCH_CHECK(_e == hipSuccess, "HIP error: ", hipGetErrorString(_e)); \
-  } while (0)
 
 namespace {
 
@@ -59,24 +53,20 @@ __device__ __forceinline__ void st(__hip_bfloat16* p, float v) {
   *p = __float2bfloat16(v);
 }
 
-inline hipStream_t current_stream() {
-  return at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-}
-
 // ---------------------------------------------------------------------------
 // CSR SpMM: out[r, fchunk] = scale[r] * sum_e feat[indices[e], fchunk]
-// One wave per (row, chunk) pair, grid-stride. VEC in {4, 2, 1}.
+// One wave per (row, chunk) pair, grid-stride. VEC in {8, 4, 2, 1}.
 // ---------------------------------------------------------------------------
 
-// CHUNK_OUTER: iterate column panels as the SLOWEST dimension so all
-// resident waves gather from one feature panel (num_src × 64·VEC cols) at a
-// time — the panel stays Infinity-Cache(L3, 256 MiB)-resident and the random
-// neighbor-row gathers become L3 hits instead of HBM reads. With chunk
-// fastest (CHUNK_OUTER=false) every panel streams concurrently and the
-// combined working set thrashes L3.  HAS_SRC_SCALE fuses a per-source-row
-// scale (the transpose/backward SpMM's D^{-1} pre-scale) into the gather.
-template <typename T, int VEC, bool CHUNK_OUTER, bool HAS_SRC_SCALE,
-          bool U8 = false>
+// Chunk-inner order (consecutive waves take the chunks of one row): sweeping
+// one column panel at a time to keep it cache-resident measured slower at
+// every shape (42.7 -> 49.8 ms at F=602; profiles/README.md).
+// 4 gathers in flight per lane are enough: 8 measured neutral and a wave that
+// walks a whole row 2x slower — wave-level parallelism, not per-wave depth,
+// hides the gather latency (profiles/README.md, negative results).
+// HAS_SRC_SCALE fuses a per-source-row scale (the transpose/backward SpMM's
+// D^{-1} pre-scale) into the gather.
+template <typename T, int VEC, bool HAS_SRC_SCALE>
 __global__ void spmm_csr_kernel(const int64_t* __restrict__ indptr,
                                 const int32_t* __restrict__ indices,
                                 const T* __restrict__ feat,
@@ -93,14 +83,8 @@ __global__ void spmm_csr_kernel(const int64_t* __restrict__ indptr,
   const int64_t npairs = num_rows * nchunks;
 
   for (int64_t pair = wave_global; pair < npairs; pair += nwaves) {
-    int64_t r, chunk;
-    if (CHUNK_OUTER) {
-      r = pair % num_rows;
-      chunk = pair / num_rows;
-    } else {
-      r = pair / nchunks;
-      chunk = pair % nchunks;
-    }
+    int64_t r = pair / nchunks;
+    const int64_t chunk = pair % nchunks;
     // LPT scheduling: rows pre-sorted by degree descending — the heavy
     // (lognormal-tail) rows start first, light rows backfill
     if (row_order) r = row_order[r];
@@ -127,32 +111,6 @@ __global__ void spmm_csr_kernel(const int64_t* __restrict__ indptr,
 #pragma unroll
         for (int k = 0; k < VEC; ++k)
           acc[k] += s * to_f32(feat[u * F + f0 + k]);
-      }
-      if (U8) {
-        // 8 outstanding gathers per wave instead of 4 (recorded
-        // experiment, PIPEGCN_SPMM_U8 — see host-side note: neutral)
-        for (; e + 8 <= e_end; e += 8) {
-          const int32x4 ua = __builtin_nontemporal_load(
-              reinterpret_cast<const int32x4*>(indices + e));
-          const int32x4 ub = __builtin_nontemporal_load(
-              reinterpret_cast<const int32x4*>(indices + e + 4));
-          const int64_t u[8] = {ua[0], ua[1], ua[2], ua[3],
-                                ub[0], ub[1], ub[2], ub[3]};
-          float sc[8];
-#pragma unroll
-          for (int j = 0; j < 8; ++j)
-            sc[j] = HAS_SRC_SCALE ? src_scale[u[j]] : 1.f;
-          float v[8][VEC];
-#pragma unroll
-          for (int j = 0; j < 8; ++j)
-#pragma unroll
-            for (int k = 0; k < VEC; ++k)
-              v[j][k] = to_f32(feat[u[j] * F + f0 + k]);
-#pragma unroll
-          for (int j = 0; j < 8; ++j)
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) acc[k] += sc[j] * v[j][k];
-        }
       }
       for (; e + 4 <= e_end; e += 4) {
         const int32x4 uu = __builtin_nontemporal_load(
@@ -212,163 +170,28 @@ __global__ void spmm_csr_kernel(const int64_t* __restrict__ indptr,
   }
 }
 
-// Multi-chunk variant (MEASURED NEGATIVE — kept env-gated as a recorded
-// experiment, PIPEGCN_SPMM_NC=8): ONE wave walks a row's edge list once and
-// covers up to NC column chunks, reading the index list once and turning
-// each edge's gathers into NC back-to-back requests on one contiguous
-// feature row. Measured 2.0-2.2x SLOWER than the chunk-per-wave default
-// (F=602: 41->80 ms; F=256: 15.5->31.5 ms, with 4-edge index lookahead):
-// concentrating the same gather instructions into NC-fold fewer waves
-// trades away wave-level parallelism, which on MI355X hides gather latency
-// far better than intra-wave ILP does.
-template <typename T, int VEC, int NC, bool HAS_SRC_SCALE>
-__global__ void spmm_csr_mc_kernel(const int64_t* __restrict__ indptr,
-                                   const int32_t* __restrict__ indices,
-                                   const T* __restrict__ feat,
-                                   const float* __restrict__ dst_scale,
-                                   const float* __restrict__ src_scale,
-                                   const int32_t* __restrict__ row_order,
-                                   T* __restrict__ out, int64_t num_rows,
-                                   int64_t F, int64_t ngroups) {
-  const int64_t wave_global =
-      (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / kWave;
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t nwaves =
-      (static_cast<int64_t>(gridDim.x) * blockDim.x) / kWave;
-  const int64_t npairs = num_rows * ngroups;
-
-  for (int64_t pair = wave_global; pair < npairs; pair += nwaves) {
-    int64_t r = pair / ngroups;
-    const int64_t grp = pair % ngroups;
-    if (row_order) r = row_order[r];
-    const int64_t base =
-        grp * NC * (kWave * VEC) + static_cast<int64_t>(lane) * VEC;
-    if (base >= F) continue;
-
-    float acc[NC][VEC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) acc[c][k] = 0.f;
-
-    const int64_t e_end = indptr[r + 1];
-    int64_t e = indptr[r];
-    auto body = [&](int64_t u) {
-      const float s = HAS_SRC_SCALE ? src_scale[u] : 1.f;
-      const T* frow = feat + u * F;
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const int64_t f = base + c * (kWave * VEC);
-        if (f + VEC <= F) {
-#pragma unroll
-          for (int k = 0; k < VEC; ++k)
-            acc[c][k] += s * to_f32(frow[f + k]);
-        } else if (f < F) {
-          for (int k = 0; f + k < F; ++k)
-            acc[c][k] += s * to_f32(frow[f + k]);
-        }
-      }
-    };
-    // 4-edge lookahead: one dwordx4 index load feeds 4 edges of gathers so
-    // the index-load latency is off the per-edge critical path
-    for (; e < e_end && (e & 3); ++e)
-      body(__builtin_nontemporal_load(indices + e));
-    for (; e + 4 <= e_end; e += 4) {
-      const int32x4 uu = __builtin_nontemporal_load(
-          reinterpret_cast<const int32x4*>(indices + e));
-      body(uu[0]);
-      body(uu[1]);
-      body(uu[2]);
-      body(uu[3]);
-    }
-    for (; e < e_end; ++e)
-      body(__builtin_nontemporal_load(indices + e));
-    const float s = dst_scale ? dst_scale[r] : 1.f;
-    T* orow = out + r * F;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int64_t f = base + c * (kWave * VEC);
-      if (f + VEC <= F) {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) st_nt(orow + f + k, acc[c][k] * s);
-      } else if (f < F) {
-        for (int k = 0; f + k < F; ++k) st(orow + f + k, acc[c][k] * s);
-      }
-    }
-  }
-}
-
-template <typename T, int VEC>
-void launch_spmm_mc(const int64_t* indptr, const int32_t* indices,
-                    const T* feat, const float* dst_scale,
-                    const float* src_scale, const int32_t* row_order, T* out,
-                    int64_t num_rows, int64_t F, hipStream_t stream) {
-  constexpr int NC = 8;
-  const int64_t nchunks = (F + kWave * VEC - 1) / (kWave * VEC);
-  const int64_t ngroups = (nchunks + NC - 1) / NC;
-  const int threads = 256;
-  int64_t blocks = (num_rows * ngroups * kWave + threads - 1) / threads;
-  blocks = std::min<int64_t>(blocks, 8 * 65536);
-  if (blocks == 0) blocks = 1;
-  auto launch = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), 0, stream, indptr,
-                       indices, feat, dst_scale, src_scale, row_order, out,
-                       num_rows, F, ngroups);
-  };
-  if (src_scale)
-    launch(HIP_KERNEL_NAME(spmm_csr_mc_kernel<T, VEC, NC, true>));
-  else
-    launch(HIP_KERNEL_NAME(spmm_csr_mc_kernel<T, VEC, NC, false>));
-  HIP_CHECK(hipGetLastError());
-}
-
 template <typename T, int VEC>
 void launch_spmm(const int64_t* indptr, const int32_t* indices,
                  const T* feat, const float* dst_scale,
                  const float* src_scale, const int32_t* row_order, T* out,
-                 int64_t num_src, int64_t num_rows, int64_t F,
-                 bool chunk_outer, hipStream_t stream) {
+                 int64_t num_rows, int64_t F, hipStream_t stream) {
   const int64_t nchunks = (F + kWave * VEC - 1) / (kWave * VEC);
   const int threads = 256;  // 4 waves
   const int64_t npairs = num_rows * nchunks;
   int64_t blocks = (npairs * kWave + threads - 1) / threads;
-  // MI355X: 256 CUs; cap the grid, grid-stride covers the rest. For
-  // chunk-outer panel locality the wave front must sweep rows in order, so
-  // cap at full residency (256 CU × 8 blocks ≈ upper bound).
-  blocks = std::min<int64_t>(blocks, chunk_outer ? 4096 : 8 * 65536);
+  // cap the grid; the grid-stride loop covers the rest
+  blocks = std::min<int64_t>(blocks, 8 * 65536);
   if (blocks == 0) blocks = 1;
   auto launch = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), 0, stream, indptr,
                        indices, feat, dst_scale, src_scale, row_order, out,
                        num_rows, F, nchunks);
   };
-  // PIPEGCN_SPMM_U8=1 switches to the 8-edge inner loop — measured
-  // NEUTRAL-to-slightly-negative (F=602 fwd 41.2 -> 42.1 ms, F=256
-  // 15.5 -> 15.4): the compiler already software-pipelines the 4-edge
-  // loop's gathers, so per-wave MLP was not the limiter; the 3.8 TB/s
-  // actual-HBM plateau (PMC, profiles/README.md) is DRAM efficiency on
-  // random 512 B row-slice reads, not issue or in-flight depth.
-  static const bool u8 = [] {
-    const char* s = std::getenv("PIPEGCN_SPMM_U8");
-    return s && s[0] == '1';
-  }();
-  if (chunk_outer) {
-    if (src_scale)
-      launch(u8 ? HIP_KERNEL_NAME(spmm_csr_kernel<T, VEC, true, true, true>)
-                : HIP_KERNEL_NAME(spmm_csr_kernel<T, VEC, true, true>));
-    else
-      launch(u8 ? HIP_KERNEL_NAME(spmm_csr_kernel<T, VEC, true, false, true>)
-                : HIP_KERNEL_NAME(spmm_csr_kernel<T, VEC, true, false>));
-  } else {
-    if (src_scale)
-      launch(u8 ? HIP_KERNEL_NAME(spmm_csr_kernel<T, VEC, false, true, true>)
-                : HIP_KERNEL_NAME(spmm_csr_kernel<T, VEC, false, true>));
-    else
-      launch(u8
-                 ? HIP_KERNEL_NAME(spmm_csr_kernel<T, VEC, false, false, true>)
-                 : HIP_KERNEL_NAME(spmm_csr_kernel<T, VEC, false, false>));
-  }
-  HIP_CHECK(hipGetLastError());
+  if (src_scale)
+    launch(HIP_KERNEL_NAME(spmm_csr_kernel<T, VEC, true>));
+  else
+    launch(HIP_KERNEL_NAME(spmm_csr_kernel<T, VEC, false>));
+  check_launch();
 }
 
 // ---------------------------------------------------------------------------
@@ -423,7 +246,7 @@ void launch_rowcopy(const T* src, const int64_t* idx, T* dst,
   hipLaunchKernelGGL(HIP_KERNEL_NAME(rowcopy_kernel<T, VEC, SCATTER_ADD>),
                      dim3(blocks), dim3(threads), 0, stream, src, idx, dst,
                      nrows, F, nchunks);
-  HIP_CHECK(hipGetLastError());
+  check_launch();
 }
 
 // ---------------------------------------------------------------------------
@@ -513,52 +336,16 @@ int pick_vec(int64_t F, int64_t num_rows, int64_t elem_size = 4) {
 template <typename T>
 void spmm_dispatch(torch::Tensor& indptr, torch::Tensor& indices,
                    torch::Tensor& feat, const float* dsp, const float* ssp,
-                   const int32_t* rop, torch::Tensor& out, int64_t num_src,
-                   int64_t num_rows, int64_t F, int vec, bool chunk_outer,
-                   hipStream_t stream) {
+                   const int32_t* rop, torch::Tensor& out, int64_t num_rows,
+                   int64_t F, int vec, hipStream_t stream) {
   const T* fp = reinterpret_cast<const T*>(feat.data_ptr());
   T* op = reinterpret_cast<T*>(out.data_ptr());
   const int64_t* ip = indptr.data_ptr<int64_t>();
   const int32_t* xp = indices.data_ptr<int32_t>();
-  if (const char* e = std::getenv("PIPEGCN_SPMM_NC")) {
-    if (std::atoi(e) == 8) {  // experimental whole-row multi-chunk variant
-      switch (vec) {
-        case 8:
-          launch_spmm_mc<T, 8>(ip, xp, fp, dsp, ssp, rop, op, num_rows, F,
-                               stream);
-          return;
-        case 4:
-          launch_spmm_mc<T, 4>(ip, xp, fp, dsp, ssp, rop, op, num_rows, F,
-                               stream);
-          return;
-        case 2:
-          launch_spmm_mc<T, 2>(ip, xp, fp, dsp, ssp, rop, op, num_rows, F,
-                               stream);
-          return;
-        default:
-          launch_spmm_mc<T, 1>(ip, xp, fp, dsp, ssp, rop, op, num_rows, F,
-                               stream);
-          return;
-      }
-    }
-  }
-  switch (vec) {
-    case 8:
-      launch_spmm<T, 8>(ip, xp, fp, dsp, ssp, rop, op, num_src, num_rows, F,
-                        chunk_outer, stream);
-      break;
-    case 4:
-      launch_spmm<T, 4>(ip, xp, fp, dsp, ssp, rop, op, num_src, num_rows, F,
-                        chunk_outer, stream);
-      break;
-    case 2:
-      launch_spmm<T, 2>(ip, xp, fp, dsp, ssp, rop, op, num_src, num_rows, F,
-                        chunk_outer, stream);
-      break;
-    default:
-      launch_spmm<T, 1>(ip, xp, fp, dsp, ssp, rop, op, num_src, num_rows, F,
-                        chunk_outer, stream);
-  }
+  dispatch_vec(vec, [&](auto v) {
+    launch_spmm<T, v.value>(ip, xp, fp, dsp, ssp, rop, op, num_rows, F,
+                            stream);
+  });
 }
 
 void spmm_csr_hip(torch::Tensor indptr, torch::Tensor indices,
@@ -597,16 +384,12 @@ void spmm_csr_hip(torch::Tensor indptr, torch::Tensor indices,
   }
   auto stream = current_stream();
   const int vec = pick_vec(F, num_rows, bf16 ? 2 : 4);
-  bool chunk_outer = false;  // measured: chunk-inner wins at every shape
-  if (const char* e = std::getenv("PIPEGCN_SPMM_ORDER"))
-    chunk_outer = (e[0] == 'o');
   if (bf16)
     spmm_dispatch<__hip_bfloat16>(indptr, indices, feat, dsp, ssp, rop, out,
-                                  num_src, num_rows, F, vec, chunk_outer,
-                                  stream);
+                                  num_rows, F, vec, stream);
   else
-    spmm_dispatch<float>(indptr, indices, feat, dsp, ssp, rop, out, num_src,
-                         num_rows, F, vec, chunk_outer, stream);
+    spmm_dispatch<float>(indptr, indices, feat, dsp, ssp, rop, out, num_rows,
+                         F, vec, stream);
 }
 
 template <typename T, bool SCATTER_ADD>
@@ -616,19 +399,9 @@ void rowcopy_dispatch(torch::Tensor& src, torch::Tensor& idx,
   const T* sp = reinterpret_cast<const T*>(src.data_ptr());
   T* dp = reinterpret_cast<T*>(dst.data_ptr());
   const int64_t* ixp = idx.data_ptr<int64_t>();
-  switch (vec) {
-    case 8:
-      launch_rowcopy<T, 8, SCATTER_ADD>(sp, ixp, dp, n, F, stream);
-      break;
-    case 4:
-      launch_rowcopy<T, 4, SCATTER_ADD>(sp, ixp, dp, n, F, stream);
-      break;
-    case 2:
-      launch_rowcopy<T, 2, SCATTER_ADD>(sp, ixp, dp, n, F, stream);
-      break;
-    default:
-      launch_rowcopy<T, 1, SCATTER_ADD>(sp, ixp, dp, n, F, stream);
-  }
+  dispatch_vec(vec, [&](auto v) {
+    launch_rowcopy<T, v.value, SCATTER_ADD>(sp, ixp, dp, n, F, stream);
+  });
 }
 
 void gather_rows_hip(torch::Tensor src, torch::Tensor idx, torch::Tensor out) {
@@ -679,20 +452,15 @@ torch::Tensor colsum_hip(torch::Tensor x) {
   const int64_t rows_per_blk = (M + nblk - 1) / nblk;
   auto partials = torch::empty({nblk, F}, x.options());
   auto stream = current_stream();
-  const int vec = F % 4 == 0 ? 4 : (F % 2 == 0 ? 2 : 1);
-  if (vec == 4)
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(colsum_partial_kernel<4>), dim3(nblk),
-                       dim3(256), 0, stream, x.data_ptr<float>(),
-                       partials.data_ptr<float>(), M, F, rows_per_blk);
-  else if (vec == 2)
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(colsum_partial_kernel<2>), dim3(nblk),
-                       dim3(256), 0, stream, x.data_ptr<float>(),
-                       partials.data_ptr<float>(), M, F, rows_per_blk);
-  else
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(colsum_partial_kernel<1>), dim3(nblk),
-                       dim3(256), 0, stream, x.data_ptr<float>(),
-                       partials.data_ptr<float>(), M, F, rows_per_blk);
-  HIP_CHECK(hipGetLastError());
+  // widths 4, 2, 1 only: an 8-wide colsum is never picked
+  dispatch_vec(F % 4 == 0 ? 4 : (F % 2 == 0 ? 2 : 1), [&](auto v) {
+    if constexpr (v.value <= 4)
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(colsum_partial_kernel<v.value>),
+                         dim3(nblk), dim3(256), 0, stream,
+                         x.data_ptr<float>(), partials.data_ptr<float>(), M,
+                         F, rows_per_blk);
+  });
+  check_launch();
   return partials.sum(0);
 }
 
@@ -707,5 +475,5 @@ void ema_update_hip(torch::Tensor avg, torch::Tensor x, double momentum) {
   hipLaunchKernelGGL(ema_kernel, dim3(blocks), dim3(threads), 0,
                      current_stream(), avg.data_ptr<float>(),
                      x.data_ptr<float>(), static_cast<float>(momentum), n);
-  HIP_CHECK(hipGetLastError());
+  check_launch();
 }

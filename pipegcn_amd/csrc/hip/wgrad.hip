@@ -13,26 +13,25 @@
 // reproducible across runs).
 //
 // Uses v_mfma_f32_32x32x2_f32 (f32 in / f32 accumulate — an exact fmaf
-// chain, no TF32; cdna_hip_programming.md §3). Block: 256 threads,
-// BNxBK output tile (64x64 default; see the host-side note on why the
-// lower-traffic 128x128 variant measured SLOWER), 4 waves in a 2x2
-// quadrant layout,
-// FN x FK 32x32 fragments per wave per product; M staged through LDS 32
-// rows at a time (+1-dword row padding against bank conflicts).
+// chain, no TF32). Block: 256 threads, 64x64 output tile, 4 waves in a 2x2
+// quadrant layout, one 32x32 fragment per wave per product; M staged
+// through LDS 32 rows at a time (+1-dword row padding against bank
+// conflicts). A 128x128 tile halves HBM re-reads but measured SLOWER
+// (66->57 TF at [233k]x[256,602]): its 128 accumulator VGPRs per wave drop
+// occupancy, and the kernel is latency-, not bandwidth-, bound here.
 // x2 == nullptr computes gw1 only (tail linears, GCN).
 
 #include "../common.h"
+#include "hip_util.h"
 
-#include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 #include <hip/hip_runtime.h>
-
-#include <cstdlib>
 
 namespace {
 
-using f32x16 = __attribute__((__vector_size__(16 * sizeof(float)))) float;
+constexpr int BN = 64;  // output tile rows per block (N of g)
+constexpr int BK = 64;  // output tile cols per block (K of x)
 
-template <bool DUAL, int BN, int BK>
+template <bool DUAL>
 __global__ __launch_bounds__(256) void dual_wgrad_kernel(
     const float* __restrict__ g, const float* __restrict__ x1,
     const float* __restrict__ x2, float* __restrict__ ws1,
@@ -131,8 +130,7 @@ __global__ __launch_bounds__(256) void dual_wgrad_kernel(
     __syncthreads();
   }
 
-  // epilogue: C layout for 32x32 shapes (same as dual_gemm.hip):
-  // col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
+  // epilogue: lane holds column l31 of each fragment, rows per mfma32_c_row
   float* w1p = ws1 + static_cast<int64_t>(blockIdx.z) * N * K;
   float* w2p = DUAL ? ws2 + static_cast<int64_t>(blockIdx.z) * N * K
                     : nullptr;
@@ -144,8 +142,8 @@ __global__ __launch_bounds__(256) void dual_wgrad_kernel(
       if (col >= K) continue;
 #pragma unroll
       for (int reg = 0; reg < 16; ++reg) {
-        const int64_t row = n0 + wr * (BN / 2) + fn * 32 + (reg & 3) +
-                            8 * (reg >> 2) + 4 * lk;
+        const int64_t row =
+            n0 + wr * (BN / 2) + fn * 32 + mfma32_c_row(reg, lk);
         if (row < N) {
           w1p[row * K + col] = acc1[fn][fk][reg];
           if (DUAL) w2p[row * K + col] = acc2[fn][fk][reg];
@@ -170,16 +168,6 @@ std::vector<torch::Tensor> dual_wgrad_hip(torch::Tensor g, torch::Tensor x1,
     TORCH_CHECK(x2.is_contiguous() && x2.size(0) == M && x2.size(1) == K);
   }
 
-  // 64x64 tiles measured BEST everywhere: the 128x128 variant halves
-  // HBM re-reads but its 128 accumulator VGPRs per wave drop occupancy
-  // and LOSE (66->57 TF at [233k]x[256,602], 111->100 TF at K=256) —
-  // the kernel is latency-, not bandwidth-, bound at these shapes.
-  // Template retained for the record; env knob for re-measurement.
-  // PIPEGCN_WGRAD_CFG: 0 (default) 64x64, 1 -> 128x128, 2 -> 64x128
-  const char* cfg_s = std::getenv("PIPEGCN_WGRAD_CFG");
-  const int cfg = cfg_s ? std::atoi(cfg_s) : 0;
-  const int BN = cfg == 1 ? 128 : 64;
-  const int BK = cfg >= 1 ? 128 : 64;
   const int64_t tiles = ((N + BN - 1) / BN) * ((K + BK - 1) / BK);
   // enough blocks to fill 256 CUs several times over, M chunks 32-aligned
   int64_t S = std::min<int64_t>((1024 + tiles - 1) / tiles, 64);
@@ -191,34 +179,18 @@ std::vector<torch::Tensor> dual_wgrad_hip(torch::Tensor g, torch::Tensor x1,
   auto ws1 = torch::empty({S, N, K}, opt);
   auto ws2 = dual ? torch::empty({S, N, K}, opt) : torch::Tensor();
   dim3 grid((N + BN - 1) / BN, (K + BK - 1) / BK, S);
-  auto stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  float* gp = g.data_ptr<float>();
-  float* x1p = x1.data_ptr<float>();
-  float* x2p = dual ? x2.data_ptr<float>() : nullptr;
-  float* w1p = ws1.data_ptr<float>();
-  float* w2p = dual ? ws2.data_ptr<float>() : nullptr;
-#define LAUNCH_WGRAD(D, BNv, BKv)                                        \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(dual_wgrad_kernel<D, BNv, BKv>),    \
-                     grid, dim3(256), 0, stream, gp, x1p, x2p, w1p, w2p, \
-                     M, N, K, chunk)
-  if (dual) {
-    if (cfg == 1)
-      LAUNCH_WGRAD(true, 128, 128);
-    else if (cfg == 2)
-      LAUNCH_WGRAD(true, 64, 128);
-    else
-      LAUNCH_WGRAD(true, 64, 64);
-  } else {
-    if (cfg == 1)
-      LAUNCH_WGRAD(false, 128, 128);
-    else if (cfg == 2)
-      LAUNCH_WGRAD(false, 64, 128);
-    else
-      LAUNCH_WGRAD(false, 64, 64);
-  }
-#undef LAUNCH_WGRAD
-  hipError_t e = hipGetLastError();
-  TORCH_CHECK(e == hipSuccess, "HIP error: ", hipGetErrorString(e));
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, current_stream(),
+                       g.data_ptr<float>(), x1.data_ptr<float>(),
+                       dual ? x2.data_ptr<float>() : nullptr,
+                       ws1.data_ptr<float>(),
+                       dual ? ws2.data_ptr<float>() : nullptr, M, N, K, chunk);
+  };
+  if (dual)
+    launch(HIP_KERNEL_NAME(dual_wgrad_kernel<true>));
+  else
+    launch(HIP_KERNEL_NAME(dual_wgrad_kernel<false>));
+  check_launch();
   if (S == 1) {
     if (dual) return {ws1.squeeze(0), ws2.squeeze(0)};
     return {ws1.squeeze(0)};

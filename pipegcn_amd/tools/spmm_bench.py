@@ -1,6 +1,7 @@
-"""A/B microbenchmark for the SpMM kernel variants on a Reddit-shaped graph.
+"""A/B microbenchmark for the SpMM lane widths (PIPEGCN_SPMM_VEC) on a
+Reddit-shaped graph.
 
-Interleaved within-process rounds (guide §5.4 rule 24): variants alternate so
+Interleaved within-process rounds (guide §5.4 rule 24): widths alternate so
 run-to-run variance is correlated. Reports ms and effective (logical) GB/s =
 edges * F * 4 / t.
 
@@ -47,40 +48,32 @@ def main():
         feat = torch.randn(n, F, device="cuda")
         if args.dtype == "bf16":
             feat = feat.to(torch.bfloat16)
-        variants = []
-        for vec in (8, 4, 2, 1):
-            if F % vec or vec * elem > 16:
-                continue
-            for order in ("o", "i"):
-                variants.append((vec, order))
+        variants = [vec for vec in (8, 4, 2, 1)
+                    if F % vec == 0 and vec * elem <= 16]
         results = {v: [] for v in variants}
         ref = None
         for rnd in range(args.rounds):
-            for vec, order in variants:
+            for vec in variants:
                 os.environ["PIPEGCN_SPMM_VEC"] = str(vec)
-                os.environ["PIPEGCN_SPMM_ORDER"] = order
                 out = ops.spmm(hg.csr, feat, inv)  # warm + correctness
                 if ref is None:
                     ref = out.clone()
                 else:
                     assert torch.allclose(out.float(), ref.float(),
                                           atol=1e-4), \
-                        f"variant {vec}{order} WRONG"
+                        f"variant VEC={vec} WRONG"
                 torch.cuda.synchronize()
                 t0 = time.time()
                 for _ in range(args.iters):
                     ops.spmm(hg.csr, feat, inv)
                 torch.cuda.synchronize()
-                results[(vec, order)].append((time.time() - t0) / args.iters)
+                results[vec].append((time.time() - t0) / args.iters)
         print(f"F={F}:")
-        for (vec, order), ts in results.items():
+        for vec, ts in results.items():
             ms = min(ts) * 1e3
             gbs = E * F * elem / min(ts) / 1e9
-            tag = "chunk-outer" if order == "o" else "chunk-inner"
-            print(f"  VEC={vec} {tag:12s}: {ms:8.2f} ms  "
-                  f"{gbs:8.0f} GB/s logical")
+            print(f"  VEC={vec}: {ms:8.2f} ms  {gbs:8.0f} GB/s logical")
         os.environ.pop("PIPEGCN_SPMM_VEC")
-        os.environ.pop("PIPEGCN_SPMM_ORDER")
 
 
 if __name__ == "__main__":

@@ -142,7 +142,11 @@ def _src_scale_check(device):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("m,k,n", [(1000, 602, 256), (777, 256, 256),
-                                   (555, 256, 41), (130, 33, 17)])
+                                   (555, 256, 41), (130, 33, 17),
+                                   # N >= 64, K <= 256: forward, dgrad and
+                                   # wgrad all MFMA, with an edge tile in N
+                                   (130, 33, 64), (257, 130, 96),
+                                   (129, 64, 200)])
 def test_sage_dual_gemm_gpu(m, k, n):
     torch.manual_seed(m + k + n)
     x1 = torch.randn(m, k, device="cuda", requires_grad=True)
@@ -165,6 +169,22 @@ def test_sage_dual_gemm_gpu(m, k, n):
     assert torch.allclose(gx1, x1.grad, atol=1e-3, rtol=1e-3)
     assert torch.allclose(gx2, x2.grad, atol=1e-3, rtol=1e-3)
     assert torch.allclose(gw1, l1.weight.grad, atol=1e-2, rtol=1e-3)
+
+
+@pytest.mark.gpu
+def test_sage_dual_gemm_no_bias_gpu():
+    """bias=False reaches the MFMA epilogue's bias == nullptr branch."""
+    m, k, n = 130, 33, 64
+    torch.manual_seed(m + k + n)
+    x1 = torch.randn(m, k, device="cuda")
+    x2 = torch.randn(m, k, device="cuda")
+    l1 = torch.nn.Linear(k, n, bias=False).cuda()
+    l2 = torch.nn.Linear(k, n, bias=False).cuda()
+    out = ops.sage_dual_linear(x1, x2, l1, l2)
+    ref = l1(x1) + l2(x2)
+    scale = ref.abs().max()
+    assert (out - ref).abs().max() / scale < 1e-5, \
+        (out - ref).abs().max().item()
 
 
 @pytest.mark.gpu

@@ -1,4 +1,6 @@
-import os, sys, time
+"""Times the fused dual GEMM forward (double-buffered LDS staging; the
+single-buffer kernel it was measured against is gone, profiles/README.md)."""
+import sys, time
 sys.path.insert(0, ".")
 import torch
 from pipegcn_amd import native
@@ -25,6 +27,5 @@ for (M, K, N) in ((232965, 602, 256), (232965, 256, 256)):
     err = (out - ref).abs().max().item() / ref.abs().max().item()
     ms = t(lambda: nat.sage_dual_gemm(x1, x2, w1, w2, b))
     tf = 2 * 2 * M * N * K / 1e12
-    mode = "DB" if os.environ.get("PIPEGCN_GEMM_DB") == "1" else "SB"
-    print(f"{mode} M{M} K{K} N{N}: {ms:.3f} ms ({tf/ms*1e3:.0f} TF) "
+    print(f"M{M} K{K} N{N}: {ms:.3f} ms ({tf/ms*1e3:.0f} TF) "
           f"rel err {err:.2e}", flush=True)
