@@ -29,6 +29,10 @@ def create_parser(argv=None):
                         help="the number of GCN layers")
     parser.add_argument("--n-linear", "--n_linear", type=int, default=0,
                         help="the number of linear layers")
+    parser.add_argument("--n-heads", "--n_heads", type=int, default=1,
+                        help="attention heads of the hidden GAT layers "
+                             "(--model gat; must divide --n-hidden; "
+                             "extension over the reference)")
     parser.add_argument("--norm", choices=["layer", "batch", "none"],
                         default="layer", help="normalization method")
     parser.add_argument("--weight-decay", "--weight_decay", type=float,

@@ -156,5 +156,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused LayerNorm[+ReLU] -> (y, xhat, rstd)");
   m.def("layer_norm_relu_bwd", &layer_norm_relu_bwd,
         "-> (dx, dweight, dbias)");
+  // GPU-only: ops.gat_aggregate composes the CPU path from torch ops
+  m.def("gat_row_stats", &gat_row_stats_hip,
+        "per-destination log-sum-exp of the GAT edge scores -> lse");
+  m.def("gat_aggregate_fwd", &gat_aggregate_fwd_hip,
+        "edge-softmax aggregation -> (out[, zc, csum])");
+  m.def("gat_aggregate_bwd", &gat_aggregate_bwd_hip,
+        "transpose edge-softmax aggregation over the CSC -> (dz, d_el)");
   m.attr("with_hip") = true;
 }

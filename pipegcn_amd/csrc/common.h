@@ -95,6 +95,32 @@ void layer_norm_relu_bwd_hip(torch::Tensor dy, torch::Tensor xhat,
                              torch::Tensor b, bool relu, torch::Tensor dx,
                              torch::Tensor dw_part, torch::Tensor db_part);
 
+// GAT edge-softmax aggregation (csrc/hip/gat.hip). Attention weights are
+// recomputed from per-node state, alpha_uv = exp(leaky_relu(el[u] + er[v]) -
+// lse[v]); nothing of size nnz is allocated. z/g/out/zc/dz are fp32 or bf16
+// [nodes, F] with F = H * D; el/er/lse/csum/t/d_el are fp32 [nodes, H].
+// num_cols is the number of nodes the column indices may reference.
+//
+// lse[v,h] = log sum_{u in N(v)} exp(leaky_relu(el[u,h] + er[v,h])); rows
+// without edges get 0.
+torch::Tensor gat_row_stats_hip(torch::Tensor indptr, torch::Tensor indices,
+                                torch::Tensor el, torch::Tensor er,
+                                int64_t num_cols, double slope);
+// -> {out} or, with_aux, {out, zc, csum}: out[v] = sum_u alpha_uv z[u],
+// zc[v] = sum_u c_uv z[u], csum[v,h] = sum_u c_uv, c = alpha * leaky_relu'.
+std::vector<torch::Tensor> gat_aggregate_fwd_hip(
+    torch::Tensor indptr, torch::Tensor indices, torch::Tensor z,
+    torch::Tensor el, torch::Tensor er, torch::Tensor lse,
+    torch::Tensor row_order, int64_t num_cols, int64_t H, double slope,
+    bool with_aux);
+// Transpose pass; indptr/indices/row_order are the CSC (rows = sources).
+// t[v,h] = g[v,h,:] . out[v,h,:]. -> {dz, d_el}.
+std::vector<torch::Tensor> gat_aggregate_bwd_hip(
+    torch::Tensor indptr, torch::Tensor indices, torch::Tensor g,
+    torch::Tensor z, torch::Tensor el, torch::Tensor er, torch::Tensor lse,
+    torch::Tensor t, torch::Tensor row_order, int64_t num_cols, int64_t H,
+    double slope);
+
 // Fused dual GEMM for the GraphSAGE layer forward:
 //   out[M,N] = x1[M,K] @ w1[N,K]^T + x2[M,K] @ w2[N,K]^T + bias[N]
 // fp32, MFMA (v_mfma_f32_32x32x2_f32). Weights in torch Linear layout [N,K],

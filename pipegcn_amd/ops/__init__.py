@@ -128,6 +128,156 @@ def spmm_mean(graph: HaloGraph, feat: torch.Tensor,
     return _SpmmMean.apply(graph, feat, inv_deg)
 
 
+def _gat_check(csr: CSR, z, el, er, num_heads: int) -> None:
+    """Shape guards shared by both GAT paths; raised before any launch."""
+    if num_heads < 1 or z.dim() != 2 or z.shape[1] % num_heads != 0:
+        raise ValueError(
+            f"gat_aggregate: feature width {tuple(z.shape)} is not "
+            f"num_heads*D for num_heads={num_heads}")
+    if el.dim() != 2 or er.dim() != 2 or el.shape[1] != num_heads \
+            or er.shape[1] != num_heads:
+        raise ValueError(
+            f"gat_aggregate: el/er must be [nodes, {num_heads}], got "
+            f"{tuple(el.shape)} and {tuple(er.shape)}")
+    if z.shape[0] < csr.num_cols or el.shape[0] < csr.num_cols:
+        raise ValueError(
+            f"gat_aggregate: z/el have {z.shape[0]}/{el.shape[0]} rows but "
+            f"the graph references {csr.num_cols} source nodes (an "
+            "under-sized tensor would be an out-of-bounds GPU gather)")
+    if er.shape[0] != csr.num_rows:
+        raise ValueError(
+            f"gat_aggregate: er has {er.shape[0]} rows, the graph has "
+            f"{csr.num_rows} destination nodes")
+
+
+def _gat_aggregate_torch(csr: CSR, z, el, er, num_heads: int, slope: float):
+    """Edge-softmax aggregation composed from torch ops under ordinary
+    autograd: the CPU test tier and rank-0 eval. [nnz, H] temporaries are
+    fine here; the GPU path never makes them."""
+    rows = csr.num_rows
+    deg = csr.indptr[1:] - csr.indptr[:-1]
+    v = torch.repeat_interleave(torch.arange(rows, device=z.device), deg)
+    u = csr.indices.long()
+    zf = z.float().view(z.shape[0], num_heads, -1)
+    e = torch.nn.functional.leaky_relu(
+        el.float().index_select(0, u) + er.float().index_select(0, v), slope)
+    # the row maximum is a shift only (softmax is invariant to it)
+    m = torch.zeros(rows, num_heads, device=z.device).scatter_reduce(
+        0, v.unsqueeze(1).expand_as(e), e.detach(), "amax",
+        include_self=False)
+    ex = torch.exp(e - m.index_select(0, v))
+    den = torch.zeros(rows, num_heads, device=z.device).index_add(0, v, ex)
+    alpha = ex / den.index_select(0, v)
+    out = torch.zeros(rows, num_heads, zf.shape[2], device=z.device)
+    out = out.index_add(0, v, alpha.unsqueeze(-1) * zf.index_select(0, u))
+    return out.view(rows, -1).to(z.dtype)
+
+
+def _gat_forward_hip(csr: CSR, z, el, er, num_heads, slope, with_aux):
+    """row stats + aggregation on the gfx950 kernels -> (lse, out[, zc,
+    csum]). Uses csr.row_order as given (no lazy autotune here)."""
+    ro = csr.row_order if csr.row_order is not None else torch.Tensor()
+    lse = native().gat_row_stats(csr.indptr, csr.indices, el, er,
+                                 csr.num_cols, slope)
+    res = native().gat_aggregate_fwd(csr.indptr, csr.indices, z, el, er, lse,
+                                     ro, csr.num_cols, num_heads, slope,
+                                     with_aux)
+    return (lse, *res)
+
+
+class _GatAggregate(torch.autograd.Function):
+    """out[v] = sum_u softmax_u(leaky_relu(el[u] + er[v])) z[u] per head.
+
+    Saves per-node tensors only (z, el, er, lse, out and, for d_er, zc and
+    csum — all emitted by the one forward gather pass); the backward is ONE
+    gather pass over the CSC that recomputes alpha from them.
+    """
+
+    @staticmethod
+    def forward(ctx, graph: HaloGraph, z, el, er, num_heads, slope):
+        need_grad = any(ctx.needs_input_grad)
+        lse, out, *aux = _gat_forward_hip(graph.csr, z, el, er, num_heads,
+                                          slope, need_grad)
+        if need_grad:
+            ctx.save_for_backward(z, el, er, lse, out, *aux)
+        ctx.graph, ctx.num_heads, ctx.slope = graph, num_heads, slope
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        z, el, er, lse, out, zc, csum = ctx.saved_tensors
+        csc, H = ctx.graph.csc, ctx.num_heads
+        g = g.contiguous()
+        n = g.shape[0]
+        gh = g.view(n, H, -1).float()
+        # per-node per-head dots (t, d_er): elementwise passes over
+        # [num_in, F], no gather — plain torch ops
+        t = (gh * out.view(n, H, -1).float()).sum(-1)
+        d_er = (gh * zc.view(n, H, -1).float()).sum(-1) - t * csum
+        ro = csc.row_order if csc.row_order is not None else torch.Tensor()
+        dz, d_el = native().gat_aggregate_bwd(
+            csc.indptr, csc.indices, g, z, el, er, lse, t, ro, csc.num_cols,
+            H, ctx.slope)
+        if dz.shape[0] < z.shape[0]:  # rows the graph never references
+            dz = torch.cat((dz, dz.new_zeros(z.shape[0] - dz.shape[0],
+                                             dz.shape[1])))
+            d_el = torch.cat((d_el, d_el.new_zeros(
+                el.shape[0] - d_el.shape[0], H)))
+        return None, dz, d_el, d_er, None, None
+
+
+def gat_aggregate(graph: HaloGraph, z: torch.Tensor, el: torch.Tensor,
+                  er: torch.Tensor, num_heads: int,
+                  slope: float = 0.2) -> torch.Tensor:
+    """Differentiable GAT edge-softmax aggregation over the halo graph.
+
+    z [num_all, H*D] are the projected features of all local nodes, el
+    [num_all, H] / er [num_in, H] the source/destination attention terms;
+    returns out [num_in, H*D] (no bias). el/er are used in fp32 and their
+    gradients come back in the incoming dtype. Nothing of size nnz is
+    allocated on the GPU path, forward or backward (docs/DESIGN.md).
+    """
+    _gat_check(graph.csr, z, el, er, num_heads)
+    if not z.is_cuda:
+        return _gat_aggregate_torch(graph.csr, z, el, er, num_heads, slope)
+    if z.shape[0] != el.shape[0]:
+        raise ValueError("gat_aggregate: z and el must cover the same nodes")
+    return _GatAggregate.apply(graph, z.contiguous(),
+                               el.float().contiguous(),
+                               er.float().contiguous(), num_heads, slope)
+
+
+def gat_aggregate_csr(csr: CSR, z: torch.Tensor, el: torch.Tensor,
+                      er: torch.Tensor, num_heads: int,
+                      slope: float = 0.2) -> torch.Tensor:
+    """Forward-only edge-softmax aggregation over a plain CSR (full-graph
+    eval over FullGraph.csr)."""
+    _gat_check(csr, z, el, er, num_heads)
+    with torch.no_grad():
+        if not z.is_cuda:
+            return _gat_aggregate_torch(csr, z, el, er, num_heads, slope)
+        return _gat_forward_hip(csr, z.contiguous(), el.float().contiguous(),
+                                er.float().contiguous(), num_heads, slope,
+                                False)[1]
+
+
+class _BiasColsum(torch.autograd.Function):
+    """x + b with the bias gradient through the native colsum (see
+    sage_dual_linear: torch's own reduce is pathological for thin odd N)."""
+
+    @staticmethod
+    def forward(ctx, x, b):
+        return x + b
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, native().colsum(g.contiguous()).to(g.dtype)
+
+
+def add_bias(x: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    return _BiasColsum.apply(x, b)
+
+
 def gather_rows(src: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     return native().gather_rows(src.contiguous(), idx)
 

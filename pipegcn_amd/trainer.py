@@ -180,6 +180,13 @@ def create_model(layer_size, args):
         return GCN(layer_size, F.relu, args.use_pp, norm=args.norm,
                    dropout=args.dropout, n_linear=args.n_linear,
                    train_size=args.n_train)
+    if args.model == "gat":
+        from pipegcn_amd.models.gat import GAT
+
+        return GAT(layer_size, F.relu, args.use_pp, norm=args.norm,
+                   dropout=args.dropout, n_linear=args.n_linear,
+                   train_size=args.n_train,
+                   n_heads=getattr(args, "n_heads", 1))
     raise NotImplementedError(f"unknown model {args.model}")
 
 
