@@ -33,6 +33,12 @@ def create_parser(argv=None):
                         help="attention heads of the hidden GAT layers "
                              "(--model gat; must divide --n-hidden; "
                              "extension over the reference)")
+    parser.add_argument("--attn-drop", "--attn_drop", type=float,
+                        default=0.0,
+                        help="attention dropout of the GAT layers: "
+                             "probability in [0, 1) of dropping an edge's "
+                             "attention coefficient, per head, in training "
+                             "(--model gat)")
     parser.add_argument("--norm", choices=["layer", "batch", "none"],
                         default="layer", help="normalization method")
     parser.add_argument("--weight-decay", "--weight_decay", type=float,

@@ -159,9 +159,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // GPU-only: ops.gat_aggregate composes the CPU path from torch ops
   m.def("gat_row_stats", &gat_row_stats_hip,
         "per-destination log-sum-exp of the GAT edge scores -> lse");
+  // the attention-dropout arguments trail with defaults: drop_thr = 0 is no
+  // dropout, so calls without them run exactly what they ran before
   m.def("gat_aggregate_fwd", &gat_aggregate_fwd_hip,
-        "edge-softmax aggregation -> (out[, zc, csum])");
+        "edge-softmax aggregation -> (out[, zc, csum])", py::arg("indptr"),
+        py::arg("indices"), py::arg("z"), py::arg("el"), py::arg("er"),
+        py::arg("lse"), py::arg("row_order"), py::arg("num_cols"),
+        py::arg("num_heads"), py::arg("slope"), py::arg("with_aux"),
+        py::arg("drop_key") = 0, py::arg("drop_thr") = 0,
+        py::arg("drop_scale") = 1.0);
   m.def("gat_aggregate_bwd", &gat_aggregate_bwd_hip,
-        "transpose edge-softmax aggregation over the CSC -> (dz, d_el)");
+        "transpose edge-softmax aggregation over the CSC -> (dz, d_el)",
+        py::arg("indptr"), py::arg("indices"), py::arg("g"), py::arg("z"),
+        py::arg("el"), py::arg("er"), py::arg("lse"), py::arg("t"),
+        py::arg("row_order"), py::arg("num_cols"), py::arg("num_heads"),
+        py::arg("slope"), py::arg("drop_key") = 0, py::arg("drop_thr") = 0,
+        py::arg("drop_scale") = 1.0);
+  m.def("gat_dropout_keep", &gat_dropout_keep_hip,
+        "attention-dropout keep bits of explicit (u, v) ids -> bool [n, H]",
+        py::arg("u"), py::arg("v"), py::arg("num_heads"), py::arg("seed"),
+        py::arg("p"));
   m.attr("with_hip") = true;
 }

@@ -108,18 +108,29 @@ torch::Tensor gat_row_stats_hip(torch::Tensor indptr, torch::Tensor indices,
                                 int64_t num_cols, double slope);
 // -> {out} or, with_aux, {out, zc, csum}: out[v] = sum_u alpha_uv z[u],
 // zc[v] = sum_u c_uv z[u], csum[v,h] = sum_u c_uv, c = alpha * leaky_relu'.
+//
+// Attention dropout: drop_thr > 0 multiplies alpha in out/dz and c in zc/gc
+// by keep(drop_key, u, v, h) * drop_scale, where keep = hash >= drop_thr is
+// recomputed per edge and head from the endpoint ids (gat.hip); csum and the
+// backward's sum_v c*t stay unmasked. drop_key and drop_thr are 32-bit
+// values, drop_scale = 1 / (1 - p). drop_thr == 0 is today's code path.
 std::vector<torch::Tensor> gat_aggregate_fwd_hip(
     torch::Tensor indptr, torch::Tensor indices, torch::Tensor z,
     torch::Tensor el, torch::Tensor er, torch::Tensor lse,
     torch::Tensor row_order, int64_t num_cols, int64_t H, double slope,
-    bool with_aux);
+    bool with_aux, int64_t drop_key, int64_t drop_thr, double drop_scale);
 // Transpose pass; indptr/indices/row_order are the CSC (rows = sources).
 // t[v,h] = g[v,h,:] . out[v,h,:]. -> {dz, d_el}.
 std::vector<torch::Tensor> gat_aggregate_bwd_hip(
     torch::Tensor indptr, torch::Tensor indices, torch::Tensor g,
     torch::Tensor z, torch::Tensor el, torch::Tensor er, torch::Tensor lse,
     torch::Tensor t, torch::Tensor row_order, int64_t num_cols, int64_t H,
-    double slope);
+    double slope, int64_t drop_key, int64_t drop_thr, double drop_scale);
+// keep[i, h] of the edge u[i] -> v[i] (int32 ids, hashed as uint32) for the
+// 62-bit seed and rate p, computed by the kernels' device function: a probe
+// for comparing it with ops.gat_dropout_keep. -> bool [n, H].
+torch::Tensor gat_dropout_keep_hip(torch::Tensor u, torch::Tensor v, int64_t H,
+                                   int64_t seed, double p);
 
 // Fused dual GEMM for the GraphSAGE layer forward:
 //   out[M,N] = x1[M,K] @ w1[N,K]^T + x2[M,K] @ w2[N,K]^T + bias[N]

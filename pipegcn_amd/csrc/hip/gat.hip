@@ -16,6 +16,21 @@
 //                        d_el[u,h] = z[u,h,:].(sum_v c*g[v,h,:])
 //                                    - sum_v c*t[v,h]
 //
+// Attention dropout (p > 0) is applied AFTER the softmax, so alpha, c and lse
+// are unchanged and gat_row_stats is untouched. With w_uvh = keep(key, u, v,
+// h) / (1 - p), a bit recomputed per edge and head from a 32-bit hash of the
+// ENDPOINTS (the CSR and CSC passes see an edge at different positions):
+//
+//   out[v]    = sum_u w*alpha*z[u]        dz[u] = sum_v w*alpha*g[v]
+//   zc[v]     = sum_u w*c*z[u]            gc    = sum_v w*c*g[v]
+//   t[v,h]    = <g[v,h], out[v,h]>        (the dropped out)
+//   csum[v,h] = sum_u c  and  sum_v c*t[v,h]  use the UNMASKED c
+//
+// i.e. the masked weight goes into every accumulator that multiplies a
+// gathered row, the unmasked c into the two scalar sums: with
+// dL/ds_uv = c_uv * (w_uv * <g[v], z[u]> - t[v]) both d_er = <g, zc> - t*csum
+// and d_el keep their form. Duplicate (u, v) edges share one bit per head.
+//
 // The two aggregate kernels keep spmm_csr_kernel's scheduling shape (one wave
 // per (row, feature chunk), LPT row order, aligned dwordx4 index load, four
 // gathers in flight). A lane's VEC elements always belong to ONE head (VEC
@@ -30,6 +45,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <vector>
 
@@ -50,8 +66,19 @@ constexpr int kWavesPerSimd = 8;
 // staying 2-wide at 8 waves:
 // 17.2 vs 20.0 ms fp32, 9.7 vs 18.8 ms bf16 on the Reddit shape at F=256;
 // bf16 8-wide at 4 waves lost to 4-wide (11.2 ms). profiles/README.md.
-template <int VEC>
-constexpr int kBwdWaves = VEC <= 2 ? kWavesPerSimd : 5;
+//
+// The attention-dropout (DROP) instances add the hash to the per-edge work.
+// Three of them spill at the bounds above (16-32 B/lane of scratch) and get
+// one wave less, which removes the scratch: the 4-wide forward with zc/csum
+// (both dtypes) and the fp32 2-wide backward.
+template <int VEC, bool AUX, bool DROP>
+constexpr int kFwdWaves =
+    (AUX && DROP && VEC >= 4) ? kWavesPerSimd - 1 : kWavesPerSimd;
+template <typename T, int VEC, bool DROP>
+constexpr int kBwdWaves =
+    VEC > 2 ? 5
+            : (DROP && VEC == 2 && sizeof(T) == 4 ? kWavesPerSimd - 1
+                                                  : kWavesPerSimd);
 
 using int32x4 = __attribute__((ext_vector_type(4))) int;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
@@ -122,6 +149,38 @@ __device__ __forceinline__ void edge_weight(float s, float lse, float slope,
                                             float& a, float& c) {
   a = expf(leaky(s, slope) - lse);
   c = s > 0.f ? a : slope * a;
+}
+
+// Attention-dropout keep bit of (edge u -> v, head h): stateless, 32-bit
+// arithmetic only (mod 2^32). The pre-mix is linear so that each kernel
+// hoists the term of its fixed endpoint: drop_base() once per (row, lane),
+// then one multiply-add and the murmur3 finaliser per edge. Ids are hashed
+// as uint32 (no sign extension). ops.gat_dropout_keep is the bit-identical
+// torch mirror.
+constexpr uint32_t kDropMulU = 0x9E3779B1u;
+constexpr uint32_t kDropMulV = 0x85EBCA77u;
+constexpr uint32_t kDropMulH = 0xC2B2AE3Du;
+
+__device__ __forceinline__ uint32_t drop_base(uint32_t fixed_id,
+                                              uint32_t fixed_mul, uint32_t h,
+                                              uint32_t key) {
+  return fixed_id * fixed_mul + h * kDropMulH + key;
+}
+
+__device__ __forceinline__ uint32_t drop_mix(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x85EBCA6Bu;
+  x ^= x >> 13;
+  x *= 0xC2B2AE35u;
+  x ^= x >> 16;
+  return x;
+}
+
+// dropout weight of one edge: scale = 1 / (1 - p) if kept, else 0
+__device__ __forceinline__ float drop_weight(uint32_t id, uint32_t mul,
+                                             uint32_t base, uint32_t thr,
+                                             float scale) {
+  return drop_mix(id * mul + base) >= thr ? scale : 0.f;
 }
 
 // fixed-order butterfly sum: every lane ends with the same total
@@ -199,15 +258,19 @@ __global__ void gat_row_stats_kernel(const int64_t* __restrict__ indptr,
 // the same gathers (second accumulator, different scalar weight).
 // F = H * D and VEC | D, so every lane with f0 < F owns VEC whole elements of
 // one head — there is no ragged tail.
+// DROP multiplies a and the zc weight by the edge's dropout weight; csum
+// keeps the unmasked c (file header).
 // ---------------------------------------------------------------------------
-template <typename T, int VEC, bool AUX>
-__global__ void __launch_bounds__(256, kWavesPerSimd) gat_aggregate_fwd_kernel(
+template <typename T, int VEC, bool AUX, bool DROP>
+__global__ void __launch_bounds__(256, (kFwdWaves<VEC, AUX, DROP>))
+gat_aggregate_fwd_kernel(
     const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
     const T* __restrict__ z, const float* __restrict__ el,
     const float* __restrict__ er, const float* __restrict__ lse,
     const int32_t* __restrict__ row_order, T* __restrict__ out,
     T* __restrict__ zc, float* __restrict__ csum, int64_t num_rows, int64_t F,
-    int64_t H, int64_t D, int64_t nchunks, float slope) {
+    int64_t H, int64_t D, int64_t nchunks, float slope, uint32_t key,
+    uint32_t thr, float scale) {
   const int64_t wave_global =
       (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / kWave;
   const int lane = threadIdx.x & (kWave - 1);
@@ -226,6 +289,10 @@ __global__ void __launch_bounds__(256, kWavesPerSimd) gat_aggregate_fwd_kernel(
     const float lse_v = lse[r * H + h];
     const float* elh = el + h;
     const T* zf = z + f0;
+    uint32_t base = 0;
+    if constexpr (DROP)
+      base = drop_base(static_cast<uint32_t>(r), kDropMulV,
+                       static_cast<uint32_t>(h), key);
 
     float acc[VEC], accc[VEC];
     float cs = 0.f;
@@ -237,12 +304,20 @@ __global__ void __launch_bounds__(256, kWavesPerSimd) gat_aggregate_fwd_kernel(
       float a, c, v[VEC];
       ld_vec<T, VEC>(zf + u * F, v);
       edge_weight(elh[u * H] + er_v, lse_v, slope, a, c);
+      if constexpr (DROP) {
+        // csum takes the unmasked c, then a and c are masked in place
+        if (AUX) cs += c;
+        const float w = drop_weight(static_cast<uint32_t>(u), kDropMulU, base,
+                                    thr, scale);
+        a *= w;
+        c *= w;
+      }
 #pragma unroll
       for (int k = 0; k < VEC; ++k) acc[k] += a * v[k];
       if (AUX) {
 #pragma unroll
         for (int k = 0; k < VEC; ++k) accc[k] += c * v[k];
-        cs += c;
+        if constexpr (!DROP) cs += c;
       }
     };
 
@@ -267,6 +342,15 @@ __global__ void __launch_bounds__(256, kWavesPerSimd) gat_aggregate_fwd_kernel(
       edge_weight(x1 + er_v, lse_v, slope, a1, c1);
       edge_weight(x2 + er_v, lse_v, slope, a2, c2);
       edge_weight(x3 + er_v, lse_v, slope, a3, c3);
+      if constexpr (DROP) {
+        if (AUX) cs += c0 + c1 + c2 + c3;
+        const float w0 = drop_weight(uu[0], kDropMulU, base, thr, scale);
+        const float w1 = drop_weight(uu[1], kDropMulU, base, thr, scale);
+        const float w2 = drop_weight(uu[2], kDropMulU, base, thr, scale);
+        const float w3 = drop_weight(uu[3], kDropMulU, base, thr, scale);
+        a0 *= w0, a1 *= w1, a2 *= w2, a3 *= w3;
+        c0 *= w0, c1 *= w1, c2 *= w2, c3 *= w3;
+      }
 #pragma unroll
       for (int k = 0; k < VEC; ++k)
         acc[k] += a0 * v0[k] + a1 * v1[k] + a2 * v2[k] + a3 * v3[k];
@@ -274,7 +358,7 @@ __global__ void __launch_bounds__(256, kWavesPerSimd) gat_aggregate_fwd_kernel(
 #pragma unroll
         for (int k = 0; k < VEC; ++k)
           accc[k] += c0 * v0[k] + c1 * v1[k] + c2 * v2[k] + c3 * v3[k];
-        cs += c0 + c1 + c2 + c3;
+        if constexpr (!DROP) cs += c0 + c1 + c2 + c3;
       }
     }
     for (; e < e_end; ++e) one_edge(e);
@@ -298,15 +382,19 @@ __global__ void __launch_bounds__(256, kWavesPerSimd) gat_aggregate_fwd_kernel(
 // axis (a head may span several chunks). d_el_part must be zero-filled.
 // dst_state[v, h] = (er, lse, t, 0): the three per-destination scalars of an
 // edge arrive in ONE 16-byte gather instead of three 4-byte ones.
+// DROP multiplies the dz and gc weights by the edge's dropout weight; the
+// sum_v c*t term keeps the unmasked c (file header).
 // ---------------------------------------------------------------------------
-template <typename T, int VEC>
-__global__ void __launch_bounds__(256, kBwdWaves<VEC>) gat_aggregate_bwd_kernel(
+template <typename T, int VEC, bool DROP>
+__global__ void __launch_bounds__(256, (kBwdWaves<T, VEC, DROP>))
+gat_aggregate_bwd_kernel(
     const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
     const T* __restrict__ g, const T* __restrict__ z,
     const float* __restrict__ el, const f32x4* __restrict__ dst_state,
     const int32_t* __restrict__ row_order, T* __restrict__ dz,
     float* __restrict__ d_el_part, int64_t num_rows, int64_t F, int64_t H,
-    int64_t D, int64_t nchunks, float slope) {
+    int64_t D, int64_t nchunks, float slope, uint32_t key, uint32_t thr,
+    float scale) {
   const int64_t wave_global =
       (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / kWave;
   const int lane = threadIdx.x & (kWave - 1);
@@ -328,6 +416,10 @@ __global__ void __launch_bounds__(256, kBwdWaves<VEC>) gat_aggregate_bwd_kernel(
     if (active) {
       const float el_u = el[r * H + h];
       const T* gf = g + f0;
+      uint32_t base = 0;
+      if constexpr (DROP)
+        base = drop_base(static_cast<uint32_t>(r), kDropMulU,
+                         static_cast<uint32_t>(h), key);
       float acc[VEC], gc[VEC];
       float ct = 0.f;
 #pragma unroll
@@ -340,6 +432,12 @@ __global__ void __launch_bounds__(256, kBwdWaves<VEC>) gat_aggregate_bwd_kernel(
         const f32x4 d = dst_state[v * H + h];
         edge_weight(el_u + d[0], d[1], slope, a, c);
         ct += c * d[2];
+        if constexpr (DROP) {
+          const float w = drop_weight(static_cast<uint32_t>(v), kDropMulV,
+                                      base, thr, scale);
+          a *= w;
+          c *= w;
+        }
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
           acc[k] += a * gv[k];
@@ -368,6 +466,14 @@ __global__ void __launch_bounds__(256, kBwdWaves<VEC>) gat_aggregate_bwd_kernel(
         edge_weight(el_u + d2[0], d2[1], slope, a2, c2);
         edge_weight(el_u + d3[0], d3[1], slope, a3, c3);
         ct += c0 * d0[2] + c1 * d1[2] + c2 * d2[2] + c3 * d3[2];
+        if constexpr (DROP) {
+          const float w0 = drop_weight(vv[0], kDropMulV, base, thr, scale);
+          const float w1 = drop_weight(vv[1], kDropMulV, base, thr, scale);
+          const float w2 = drop_weight(vv[2], kDropMulV, base, thr, scale);
+          const float w3 = drop_weight(vv[3], kDropMulV, base, thr, scale);
+          a0 *= w0, a1 *= w1, a2 *= w2, a3 *= w3;
+          c0 *= w0, c1 *= w1, c2 *= w2, c3 *= w3;
+        }
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
           acc[k] += a0 * g0[k] + a1 * g1[k] + a2 * g2[k] + a3 * g3[k];
@@ -395,12 +501,64 @@ __global__ void __launch_bounds__(256, kBwdWaves<VEC>) gat_aggregate_bwd_kernel(
   }
 }
 
+// The keep bit on explicit id tensors (one thread per edge, all heads): lets
+// the device hash be compared with its torch mirror without building a graph.
+__global__ void gat_dropout_keep_kernel(const int32_t* __restrict__ u,
+                                        const int32_t* __restrict__ v,
+                                        bool* __restrict__ keep, int64_t n,
+                                        int64_t H, uint32_t key,
+                                        uint32_t thr) {
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+       i < n; i += stride) {
+    const uint32_t ui = static_cast<uint32_t>(u[i]);
+    const uint32_t vi = static_cast<uint32_t>(v[i]);
+    for (int64_t h = 0; h < H; ++h) {
+      // the forward's hoisting: v and h fixed, u per edge
+      const uint32_t base =
+          drop_base(vi, kDropMulV, static_cast<uint32_t>(h), key);
+      keep[i * H + h] = drop_mix(ui * kDropMulU + base) >= thr;
+    }
+  }
+}
+
 // Widest compiled instances (compiler resource remarks,
 // profiles/README.md): none uses scratch. bf16 forward-with-aux stops at 4
 // elements to stay within kWavesPerSimd's 64 VGPRs; the backward at 4.
-template <typename T, bool AUX>
+template <typename T, bool AUX, bool DROP>
 constexpr int kFwdMaxVec = (AUX && sizeof(T) == 2) ? 4 : 16 / sizeof(T);
 constexpr int kBwdMaxVec = 4;
+
+// host side of the attention dropout: the folded key, the keep threshold and
+// 1 / (1 - p). thr == 0 keeps every edge and runs the DROP = false instances.
+struct DropArgs {
+  uint32_t key;
+  uint32_t thr;
+  float scale;
+};
+
+DropArgs drop_args(int64_t key, int64_t thr, double scale) {
+  TORCH_CHECK(key >= 0 && key <= 0xFFFFFFFFll && thr >= 0 &&
+                  thr <= 0xFFFFFFFFll,
+              "gat: drop_key and drop_thr are 32-bit values");
+  return {static_cast<uint32_t>(key), static_cast<uint32_t>(thr),
+          static_cast<float>(scale)};
+}
+
+// low word of splitmix64(seed): the 32-bit key of one call's masks
+uint32_t drop_fold_seed(int64_t seed) {
+  uint64_t x = static_cast<uint64_t>(seed) + 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  x ^= x >> 31;
+  return static_cast<uint32_t>(x);
+}
+
+// thr = min(round(p * 2^32), 2^32 - 1); an edge is kept when hash >= thr
+uint32_t drop_threshold(double p) {
+  const double t = std::floor(p * 4294967296.0 + 0.5);
+  return t >= 4294967295.0 ? 0xFFFFFFFFu : static_cast<uint32_t>(t);
+}
 
 int64_t grid_for(int64_t nwaves, int threads) {
   int64_t blocks = (nwaves * kWave + threads - 1) / threads;
@@ -511,36 +669,43 @@ static void fwd_dispatch(const torch::Tensor& indptr,
                          const torch::Tensor& lse, const int32_t* rop,
                          torch::Tensor& out, torch::Tensor& zc,
                          torch::Tensor& csum, int64_t num_rows, int64_t F,
-                         int64_t H, bool with_aux, float slope) {
+                         int64_t H, bool with_aux, float slope,
+                         DropArgs drop) {
   const int64_t D = F / H;
   const T* zp = reinterpret_cast<const T*>(z.data_ptr());
   T* op = reinterpret_cast<T*>(out.data_ptr());
   T* zcp = with_aux ? reinterpret_cast<T*>(zc.data_ptr()) : nullptr;
   float* csp = with_aux ? csum.data_ptr<float>() : nullptr;
-  const int vec = gat_pick_vec(
-      D, sizeof(T), with_aux ? kFwdMaxVec<T, true> : kFwdMaxVec<T, false>,
-      {zp, op, zcp});
   auto stream = current_stream();
-  dispatch_vec(vec, [&](auto v) {
-    constexpr int VEC = decltype(v)::value;
-    const int64_t nchunks = (F + kWave * VEC - 1) / (kWave * VEC);
-    const int threads = 256;
-    const dim3 grid(grid_for(num_rows * nchunks, threads));
-    auto launch = [&](auto kern) {
-      hipLaunchKernelGGL(kern, grid, dim3(threads), 0, stream,
-                         indptr.data_ptr<int64_t>(),
-                         indices.data_ptr<int32_t>(), zp, el.data_ptr<float>(),
-                         er.data_ptr<float>(), lse.data_ptr<float>(), rop, op,
-                         zcp, csp, num_rows, F, H, D, nchunks, slope);
-    };
-    if (with_aux) {
-      if constexpr (VEC <= kFwdMaxVec<T, true>)
-        launch(HIP_KERNEL_NAME(gat_aggregate_fwd_kernel<T, VEC, true>));
-    } else {
-      if constexpr (VEC <= kFwdMaxVec<T, false>)
-        launch(HIP_KERNEL_NAME(gat_aggregate_fwd_kernel<T, VEC, false>));
-    }
-  });
+  auto run = [&](auto aux_c, auto drop_c) {
+    constexpr bool AUX = decltype(aux_c)::value;
+    constexpr bool DROP = decltype(drop_c)::value;
+    const int vec =
+        gat_pick_vec(D, sizeof(T), kFwdMaxVec<T, AUX, DROP>, {zp, op, zcp});
+    dispatch_vec(vec, [&](auto v) {
+      constexpr int VEC = decltype(v)::value;
+      if constexpr (VEC <= kFwdMaxVec<T, AUX, DROP>) {
+        const int64_t nchunks = (F + kWave * VEC - 1) / (kWave * VEC);
+        const int threads = 256;
+        hipLaunchKernelGGL(
+            HIP_KERNEL_NAME(gat_aggregate_fwd_kernel<T, VEC, AUX, DROP>),
+            dim3(grid_for(num_rows * nchunks, threads)), dim3(threads), 0,
+            stream, indptr.data_ptr<int64_t>(), indices.data_ptr<int32_t>(),
+            zp, el.data_ptr<float>(), er.data_ptr<float>(),
+            lse.data_ptr<float>(), rop, op, zcp, csp, num_rows, F, H, D,
+            nchunks, slope, drop.key, drop.thr, drop.scale);
+      }
+    });
+  };
+  const bool dropping = drop.thr > 0;
+  if (with_aux && dropping)
+    run(std::true_type{}, std::true_type{});
+  else if (with_aux)
+    run(std::true_type{}, std::false_type{});
+  else if (dropping)
+    run(std::false_type{}, std::true_type{});
+  else
+    run(std::false_type{}, std::false_type{});
   check_launch();
 }
 
@@ -548,8 +713,9 @@ std::vector<torch::Tensor> gat_aggregate_fwd_hip(
     torch::Tensor indptr, torch::Tensor indices, torch::Tensor z,
     torch::Tensor el, torch::Tensor er, torch::Tensor lse,
     torch::Tensor row_order, int64_t num_cols, int64_t H, double slope,
-    bool with_aux) {
+    bool with_aux, int64_t drop_key, int64_t drop_thr, double drop_scale) {
   check_graph(indptr, indices);
+  const DropArgs drop = drop_args(drop_key, drop_thr, drop_scale);
   const int64_t num_rows = indptr.numel() - 1;
   check_features(z, num_cols, H, "z");
   const int64_t F = z.size(1);
@@ -566,10 +732,11 @@ std::vector<torch::Tensor> gat_aggregate_fwd_hip(
   if (z.scalar_type() == torch::kBFloat16)
     fwd_dispatch<__hip_bfloat16>(indptr, indices, z, el, er, lse, rop, out, zc,
                                  csum, num_rows, F, H, with_aux,
-                                 static_cast<float>(slope));
+                                 static_cast<float>(slope), drop);
   else
     fwd_dispatch<float>(indptr, indices, z, el, er, lse, rop, out, zc, csum,
-                        num_rows, F, H, with_aux, static_cast<float>(slope));
+                        num_rows, F, H, with_aux, static_cast<float>(slope),
+                        drop);
   if (!with_aux) return {out};
   return {out, zc, csum};
 }
@@ -579,7 +746,7 @@ static torch::Tensor bwd_dispatch(
     const torch::Tensor& indptr, const torch::Tensor& indices,
     const torch::Tensor& g, const torch::Tensor& z, const torch::Tensor& el,
     const torch::Tensor& dst_state, const int32_t* rop, torch::Tensor& dz,
-    int64_t num_rows, int64_t F, int64_t H, float slope) {
+    int64_t num_rows, int64_t F, int64_t H, float slope, DropArgs drop) {
   const int64_t D = F / H;
   const T* gp = reinterpret_cast<const T*>(g.data_ptr());
   const T* zp = reinterpret_cast<const T*>(z.data_ptr());
@@ -595,13 +762,19 @@ static torch::Tensor bwd_dispatch(
       // zero-filled: a chunk writes only the heads it touches
       part = torch::zeros({num_rows, nchunks, H}, el.options());
       const int threads = 256;
-      hipLaunchKernelGGL(
-          HIP_KERNEL_NAME(gat_aggregate_bwd_kernel<T, VEC>),
-          dim3(grid_for(num_rows * nchunks, threads)), dim3(threads), 0,
-          stream, indptr.data_ptr<int64_t>(), indices.data_ptr<int32_t>(), gp,
-          zp, el.data_ptr<float>(),
-          reinterpret_cast<const f32x4*>(dst_state.data_ptr<float>()), rop,
-          dzp, part.data_ptr<float>(), num_rows, F, H, D, nchunks, slope);
+      auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(
+            kern, dim3(grid_for(num_rows * nchunks, threads)), dim3(threads),
+            0, stream, indptr.data_ptr<int64_t>(),
+            indices.data_ptr<int32_t>(), gp, zp, el.data_ptr<float>(),
+            reinterpret_cast<const f32x4*>(dst_state.data_ptr<float>()), rop,
+            dzp, part.data_ptr<float>(), num_rows, F, H, D, nchunks, slope,
+            drop.key, drop.thr, drop.scale);
+      };
+      if (drop.thr > 0)
+        launch(HIP_KERNEL_NAME(gat_aggregate_bwd_kernel<T, VEC, true>));
+      else
+        launch(HIP_KERNEL_NAME(gat_aggregate_bwd_kernel<T, VEC, false>));
     }
   });
   check_launch();
@@ -613,9 +786,10 @@ std::vector<torch::Tensor> gat_aggregate_bwd_hip(
     torch::Tensor indptr, torch::Tensor indices, torch::Tensor g,
     torch::Tensor z, torch::Tensor el, torch::Tensor er, torch::Tensor lse,
     torch::Tensor t, torch::Tensor row_order, int64_t num_cols, int64_t H,
-    double slope) {
+    double slope, int64_t drop_key, int64_t drop_thr, double drop_scale) {
   // indptr/indices are the CSC: rows = source nodes, columns = destinations
   check_graph(indptr, indices);
+  const DropArgs drop = drop_args(drop_key, drop_thr, drop_scale);
   const int64_t num_rows = indptr.numel() - 1;
   check_features(g, num_cols, H, "g");
   check_features(z, num_rows, H, "z");
@@ -640,9 +814,34 @@ std::vector<torch::Tensor> gat_aggregate_bwd_hip(
   if (z.scalar_type() == torch::kBFloat16)
     d_el = bwd_dispatch<__hip_bfloat16>(indptr, indices, g, z, el, dst_state,
                                         rop, dz, num_rows, F, H,
-                                        static_cast<float>(slope));
+                                        static_cast<float>(slope), drop);
   else
     d_el = bwd_dispatch<float>(indptr, indices, g, z, el, dst_state, rop, dz,
-                               num_rows, F, H, static_cast<float>(slope));
+                               num_rows, F, H, static_cast<float>(slope),
+                               drop);
   return {dz, d_el};
+}
+
+torch::Tensor gat_dropout_keep_hip(torch::Tensor u, torch::Tensor v, int64_t H,
+                                   int64_t seed, double p) {
+  TORCH_CHECK(u.is_cuda() && v.is_cuda() && u.is_contiguous() &&
+                  v.is_contiguous() && u.scalar_type() == torch::kInt &&
+                  v.scalar_type() == torch::kInt && u.dim() == 1 &&
+                  v.dim() == 1 && u.numel() == v.numel(),
+              "gat_dropout_keep: u and v must be contiguous int32 [n] device "
+              "tensors of one length");
+  TORCH_CHECK(H >= 1, "gat_dropout_keep: at least one head");
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "gat_dropout_keep: p must be in [0, 1)");
+  const int64_t n = u.numel();
+  auto keep = torch::empty({n, H}, u.options().dtype(torch::kBool));
+  if (n == 0) return keep;
+  const int threads = 256;
+  const int64_t blocks =
+      std::min<int64_t>((n + threads - 1) / threads, 8 * 65536);
+  hipLaunchKernelGGL(gat_dropout_keep_kernel, dim3(blocks), dim3(threads), 0,
+                     current_stream(), u.data_ptr<int32_t>(),
+                     v.data_ptr<int32_t>(), keep.data_ptr<bool>(), n, H,
+                     drop_fold_seed(seed), drop_threshold(p));
+  check_launch();
+  return keep;
 }

@@ -9,6 +9,11 @@ Layer, H heads of width D = out_feats / H, LeakyReLU slope 0.2:
     alpha = softmax over u in N(v) of leaky_relu(el[u] + er[v])   (per head)
     out[v] = sum_u alpha_uv z[u] + b
 
+In training, `attn_drop` > 0 drops each alpha_uv (per head) with that
+probability and scales the rest by 1 / (1 - attn_drop); evaluation never
+drops. The mask is recomputed inside the kernels from a hash of the edge's
+endpoints and a per-call seed drawn from torch's host generator.
+
 The aggregation is `ops.gat_aggregate` (csrc/hip/gat.hip): alpha is
 recomputed from per-node state wherever it is needed, so no [nnz, H] tensor
 exists on the GPU in forward or backward (docs/DESIGN.md). Gradients reach
@@ -31,8 +36,12 @@ NEGATIVE_SLOPE = 0.2
 
 
 class GATLayer(nn.Module):
-    def __init__(self, in_feats, out_feats, num_heads=1, bias=True):
+    def __init__(self, in_feats, out_feats, num_heads=1, bias=True,
+                 attn_drop=0.0):
         super().__init__()
+        if not 0.0 <= attn_drop < 1.0:
+            raise ValueError(f"attn_drop={attn_drop} is outside [0, 1)")
+        self.attn_drop = attn_drop
         if num_heads < 1 or out_feats % num_heads != 0:
             raise ValueError(
                 f"GAT layer width {out_feats} is not divisible by "
@@ -67,7 +76,7 @@ class GATLayer(nn.Module):
             assert isinstance(graph, HaloGraph)
             er = self._scores(z[: graph.num_in], self.attn_r)
             out = ops.gat_aggregate(graph, z, el, er, self.num_heads,
-                                    NEGATIVE_SLOPE)
+                                    NEGATIVE_SLOPE, self.attn_drop)
         else:
             # eval: full homogeneous graph, every node is a destination
             assert isinstance(graph, FullGraph)
@@ -88,7 +97,8 @@ class GAT(GNNBase):
     """
 
     def __init__(self, layer_size, activation, use_pp=False, dropout=0.5,
-                 norm="layer", train_size=None, n_linear=0, n_heads=1):
+                 norm="layer", train_size=None, n_linear=0, n_heads=1,
+                 attn_drop=0.0):
         if use_pp:
             raise NotImplementedError("--use-pp supports graphsage only "
                                       "(reference parity)")
@@ -100,7 +110,8 @@ class GAT(GNNBase):
             if i < self.n_layers - self.n_linear:
                 heads = 1 if i == self.n_layers - 1 else n_heads
                 self.layers.append(GATLayer(layer_size[i], layer_size[i + 1],
-                                            num_heads=heads))
+                                            num_heads=heads,
+                                            attn_drop=attn_drop))
             else:
                 self.layers.append(nn.Linear(layer_size[i],
                                              layer_size[i + 1]))

@@ -10,6 +10,7 @@ eager fallback on GPU); CPU tensors use the native C++ paths.
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import Optional
 
@@ -150,10 +151,63 @@ def _gat_check(csr: CSR, z, el, er, num_heads: int) -> None:
             f"{csr.num_rows} destination nodes")
 
 
-def _gat_aggregate_torch(csr: CSR, z, el, er, num_heads: int, slope: float):
+_M32 = 0xFFFFFFFF
+_M64 = 0xFFFFFFFFFFFFFFFF
+
+
+def _gat_dropout_params(seed: int, p: float):
+    """(key, thr, scale) of one attention-dropout call, as csrc/hip/gat.hip
+    derives them: key = low word of splitmix64(seed), an edge is kept when
+    its hash >= thr = min(round(p * 2^32), 2^32 - 1), scale = 1 / (1 - p)."""
+    x = (int(seed) + 0x9E3779B97F4A7C15) & _M64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
+    x ^= x >> 31
+    thr = min(int(math.floor(p * 4294967296.0 + 0.5)), _M32)
+    return x & _M32, thr, 1.0 / (1.0 - p)
+
+
+def _gat_keep_hash(u: torch.Tensor, v: torch.Tensor, num_heads: int,
+                   key: int) -> torch.Tensor:
+    """The 32-bit edge hash [n, H] as int64 values in [0, 2^32). torch's
+    int64 multiply wraps, so the low 32 bits of every step are exact."""
+    u = u.long() & _M32
+    v = v.long() & _M32
+    h = torch.arange(num_heads, dtype=torch.int64, device=u.device)
+    x = ((u * 0x9E3779B1 + v * 0x85EBCA77).unsqueeze(-1)
+         + h * 0xC2B2AE3D + key) & _M32
+    x = x ^ (x >> 16)
+    x = (x * 0x85EBCA6B) & _M32
+    x = x ^ (x >> 13)
+    x = (x * 0xC2B2AE35) & _M32
+    return x ^ (x >> 16)
+
+
+def gat_dropout_keep(u: torch.Tensor, v: torch.Tensor, num_heads: int,
+                     seed: int, p: float) -> torch.Tensor:
+    """Attention-dropout keep bits of the edges u[i] -> v[i]: bool [n, H].
+
+    The bit-identical torch mirror of the device function the GAT kernels
+    evaluate per edge (csrc/hip/gat.hip): a stateless 32-bit hash of (seed,
+    source id u, destination id v, head), kept when it is at least
+    round(p * 2^32). u and v are integer tensors of local node ids (any
+    integer dtype; only the low 32 bits count, as on the device). The bit
+    depends on the endpoints, not on the edge's position, so the CSR and the
+    CSC pass agree on it and duplicate (u, v) edges share it. Runs on the
+    tensors' device; the CPU path of `gat_aggregate` and the tests use it.
+    """
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"gat_dropout_keep: p={p} is outside [0, 1)")
+    key, thr, _ = _gat_dropout_params(seed, p)
+    return _gat_keep_hash(u, v, num_heads, key) >= thr
+
+
+def _gat_aggregate_torch(csr: CSR, z, el, er, num_heads: int, slope: float,
+                         drop=None):
     """Edge-softmax aggregation composed from torch ops under ordinary
     autograd: the CPU test tier and rank-0 eval. [nnz, H] temporaries are
-    fine here; the GPU path never makes them."""
+    fine here; the GPU path never makes them. drop = (key, thr, scale)
+    applies the attention-dropout mask the kernels would draw."""
     rows = csr.num_rows
     deg = csr.indptr[1:] - csr.indptr[:-1]
     v = torch.repeat_interleave(torch.arange(rows, device=z.device), deg)
@@ -168,20 +222,26 @@ def _gat_aggregate_torch(csr: CSR, z, el, er, num_heads: int, slope: float):
     ex = torch.exp(e - m.index_select(0, v))
     den = torch.zeros(rows, num_heads, device=z.device).index_add(0, v, ex)
     alpha = ex / den.index_select(0, v)
+    if drop is not None:
+        key, thr, scale = drop
+        keep = _gat_keep_hash(u, v, num_heads, key) >= thr
+        alpha = alpha * (keep.to(alpha.dtype) * scale)
     out = torch.zeros(rows, num_heads, zf.shape[2], device=z.device)
     out = out.index_add(0, v, alpha.unsqueeze(-1) * zf.index_select(0, u))
     return out.view(rows, -1).to(z.dtype)
 
 
-def _gat_forward_hip(csr: CSR, z, el, er, num_heads, slope, with_aux):
+def _gat_forward_hip(csr: CSR, z, el, er, num_heads, slope, with_aux,
+                     drop=(0, 0, 1.0)):
     """row stats + aggregation on the gfx950 kernels -> (lse, out[, zc,
-    csum]). Uses csr.row_order as given (no lazy autotune here)."""
+    csum]). Uses csr.row_order as given (no lazy autotune here). drop =
+    (key, thr, scale); thr 0 is no attention dropout."""
     ro = csr.row_order if csr.row_order is not None else torch.Tensor()
     lse = native().gat_row_stats(csr.indptr, csr.indices, el, er,
                                  csr.num_cols, slope)
     res = native().gat_aggregate_fwd(csr.indptr, csr.indices, z, el, er, lse,
                                      ro, csr.num_cols, num_heads, slope,
-                                     with_aux)
+                                     with_aux, *drop)
     return (lse, *res)
 
 
@@ -190,17 +250,20 @@ class _GatAggregate(torch.autograd.Function):
 
     Saves per-node tensors only (z, el, er, lse, out and, for d_er, zc and
     csum — all emitted by the one forward gather pass); the backward is ONE
-    gather pass over the CSC that recomputes alpha from them.
+    gather pass over the CSC that recomputes alpha from them. Attention
+    dropout adds three scalars (key, thr, scale) and no tensor: both passes
+    recompute the keep bits from the edge endpoints.
     """
 
     @staticmethod
-    def forward(ctx, graph: HaloGraph, z, el, er, num_heads, slope):
+    def forward(ctx, graph: HaloGraph, z, el, er, num_heads, slope, drop):
         need_grad = any(ctx.needs_input_grad)
         lse, out, *aux = _gat_forward_hip(graph.csr, z, el, er, num_heads,
-                                          slope, need_grad)
+                                          slope, need_grad, drop)
         if need_grad:
             ctx.save_for_backward(z, el, er, lse, out, *aux)
         ctx.graph, ctx.num_heads, ctx.slope = graph, num_heads, slope
+        ctx.drop = drop
         return out
 
     @staticmethod
@@ -217,18 +280,19 @@ class _GatAggregate(torch.autograd.Function):
         ro = csc.row_order if csc.row_order is not None else torch.Tensor()
         dz, d_el = native().gat_aggregate_bwd(
             csc.indptr, csc.indices, g, z, el, er, lse, t, ro, csc.num_cols,
-            H, ctx.slope)
+            H, ctx.slope, *ctx.drop)
         if dz.shape[0] < z.shape[0]:  # rows the graph never references
             dz = torch.cat((dz, dz.new_zeros(z.shape[0] - dz.shape[0],
                                              dz.shape[1])))
             d_el = torch.cat((d_el, d_el.new_zeros(
                 el.shape[0] - d_el.shape[0], H)))
-        return None, dz, d_el, d_er, None, None
+        return None, dz, d_el, d_er, None, None, None
 
 
 def gat_aggregate(graph: HaloGraph, z: torch.Tensor, el: torch.Tensor,
-                  er: torch.Tensor, num_heads: int,
-                  slope: float = 0.2) -> torch.Tensor:
+                  er: torch.Tensor, num_heads: int, slope: float = 0.2,
+                  attn_drop: float = 0.0,
+                  seed: Optional[int] = None) -> torch.Tensor:
     """Differentiable GAT edge-softmax aggregation over the halo graph.
 
     z [num_all, H*D] are the projected features of all local nodes, el
@@ -236,15 +300,34 @@ def gat_aggregate(graph: HaloGraph, z: torch.Tensor, el: torch.Tensor,
     returns out [num_in, H*D] (no bias). el/er are used in fp32 and their
     gradients come back in the incoming dtype. Nothing of size nnz is
     allocated on the GPU path, forward or backward (docs/DESIGN.md).
+
+    attn_drop in [0, 1) drops each attention coefficient (per edge and
+    head, after the softmax) with that probability and scales the kept ones
+    by 1 / (1 - attn_drop). The mask is `gat_dropout_keep(u, v, num_heads,
+    seed, attn_drop)` on local node ids, recomputed in both passes and never
+    stored; CPU and GPU draw the same mask for the same seed. seed (0 <=
+    seed < 2^62) defaults to a draw from torch's host generator, so runs are
+    reproducible under torch.manual_seed; attn_drop == 0 draws nothing.
     """
+    if not 0.0 <= attn_drop < 1.0:
+        raise ValueError(
+            f"gat_aggregate: attn_drop={attn_drop} is outside [0, 1)")
     _gat_check(graph.csr, z, el, er, num_heads)
+    drop = (0, 0, 1.0)
+    if attn_drop > 0.0:
+        if seed is None:
+            # host-drawn, as fused_dropout: no device sync
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        drop = _gat_dropout_params(seed, attn_drop)
     if not z.is_cuda:
-        return _gat_aggregate_torch(graph.csr, z, el, er, num_heads, slope)
+        return _gat_aggregate_torch(graph.csr, z, el, er, num_heads, slope,
+                                    drop if drop[1] > 0 else None)
     if z.shape[0] != el.shape[0]:
         raise ValueError("gat_aggregate: z and el must cover the same nodes")
     return _GatAggregate.apply(graph, z.contiguous(),
                                el.float().contiguous(),
-                               er.float().contiguous(), num_heads, slope)
+                               er.float().contiguous(), num_heads, slope,
+                               drop)
 
 
 def gat_aggregate_csr(csr: CSR, z: torch.Tensor, el: torch.Tensor,

@@ -15,8 +15,13 @@ each window closed by a synchronise. The trainer's own `Time(s)` log column
 closes its window before the loss is read back, so on a single GPU with no
 peers it reports launch time only and cannot serve here.
 
+`--attn-drop P` runs every GAT call with attention dropout P: the DROP
+instances of the two aggregate kernels in the kernel table (row_stats and
+the SpMM columns do not change), and GAT(attn_drop=P) under `--epoch`.
+
     python tools/microbench/gat_bench.py [--shape reddit] [--feats 256]
     python tools/microbench/gat_bench.py --epoch
+    python tools/microbench/gat_bench.py [--epoch] --attn-drop 0.6
 """
 import argparse
 import json
@@ -40,7 +45,11 @@ ap.add_argument("--iters", type=int, default=5)
 ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--epoch", action="store_true",
                 help="time whole training epochs instead of the kernels")
+ap.add_argument("--attn-drop", "--attn_drop", type=float, default=0.0,
+                help="attention dropout of every GAT call (default: none)")
 args = ap.parse_args()
+if not 0.0 <= args.attn_drop < 1.0:
+    ap.error("--attn-drop must be in [0, 1)")
 
 SLOPE = 0.2
 dev = "cuda" if torch.cuda.is_available() else "cpu"  # cpu: --epoch dry run
@@ -106,7 +115,8 @@ def epoch_bench():
         for name, cls, kw, d in (
                 ("graphsage", GraphSAGE, dict(use_pp=False), deg),
                 ("gcn", GCN, {}, deg_all),
-                ("gat-4-heads", GAT, dict(n_heads=4), None)):
+                ("gat-4-heads", GAT,
+                 dict(n_heads=4, attn_drop=args.attn_drop), None)):
             torch.manual_seed(0)
             model = cls(layer_size, Fn.relu, dropout=0.5, norm="layer",
                         train_size=part.n_train, **kw).to(dev).to(dtype)
@@ -125,6 +135,7 @@ def epoch_bench():
         ms = bench(steps)
         print(json.dumps(dict(mode="epoch", shape=args.shape, dtype=dname,
                               hidden=256, layers=3,
+                              attn_drop=args.attn_drop,
                               ms_per_epoch={k: round(v, 2)
                                             for k, v in ms.items()},
                               peak_gb=round(
@@ -146,6 +157,10 @@ if args.epoch:
     dist.destroy_process_group()
     sys.exit(0)
 
+# (key, thr, scale) of the native entry points; (0, 0, 1.0) is no dropout
+DROP_SEED = 1234
+drop = (ops._gat_dropout_params(DROP_SEED, args.attn_drop)
+        if args.attn_drop > 0 else (0, 0, 1.0))
 rows = []
 for dname in args.dtypes:
     dtype = torch.bfloat16 if dname == "bf16" else torch.float32
@@ -170,7 +185,8 @@ for dname in args.dtypes:
 
         def gat_fb():
             zr.grad = elr.grad = err.grad = None
-            ops.gat_aggregate(hg, zr, elr, err, H, SLOPE).backward(g)
+            ops.gat_aggregate(hg, zr, elr, err, H, SLOPE, args.attn_drop,
+                              DROP_SEED).backward(g)
 
         def spmm_fb():
             zr.grad = None
@@ -181,15 +197,16 @@ for dname in args.dtypes:
                 csr.indptr, csr.indices, el, er, csr.num_cols, SLOPE),
             "agg_fwd": lambda: nat.gat_aggregate_fwd(
                 csr.indptr, csr.indices, z, el, er, lse, ro, csr.num_cols, H,
-                SLOPE, False),
+                SLOPE, False, *drop),
             "agg_fwd_aux": lambda: nat.gat_aggregate_fwd(
                 csr.indptr, csr.indices, z, el, er, lse, ro, csr.num_cols, H,
-                SLOPE, True),
+                SLOPE, True, *drop),
             "agg_bwd": lambda: nat.gat_aggregate_bwd(
                 csc.indptr, csc.indices, g, z, el, er, lse, t, roc,
-                csc.num_cols, H, SLOPE),
+                csc.num_cols, H, SLOPE, *drop),
             "spmm_fwd": lambda: ops.spmm_mean(hg, z, inv),
-            "gat_fwd": lambda: ops.gat_aggregate(hg, z, el, er, H, SLOPE),
+            "gat_fwd": lambda: ops.gat_aggregate(
+                hg, z, el, er, H, SLOPE, args.attn_drop, DROP_SEED),
             "spmm_fwd_bwd": spmm_fb,
             "gat_fwd_bwd": gat_fb,
         })
@@ -198,7 +215,7 @@ for dname in args.dtypes:
         per_edge = {"row_stats": 4 + 4 * H, "agg_fwd": es * F + 4 * H + 4,
                     "agg_fwd_aux": es * F + 4 * H + 4,
                     "agg_bwd": es * F + 16 * H + 4, "spmm_fwd": es * F + 4}
-        rec = dict(dtype=dname, H=H, F=F, nnz=nnz,
+        rec = dict(dtype=dname, H=H, F=F, nnz=nnz, attn_drop=args.attn_drop,
                    ms={k: round(v, 3) for k, v in ms.items()},
                    tb_per_s={k: round(nnz * b / ms[k] / 1e9, 3)
                              for k, b in per_edge.items()},
