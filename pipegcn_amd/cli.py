@@ -14,7 +14,8 @@ def create_parser(argv=None):
     parser.add_argument("--graph-name", "--graph_name", type=str, default="")
 
     parser.add_argument("--model", type=str, default="graphsage",
-                        help="model for training")
+                        help="model for training: graphsage, gcn, gat or "
+                             "gatv2")
     parser.add_argument("--dropout", type=float, default=0.5,
                         help="dropout probability")
     parser.add_argument("--lr", type=float, default=1e-2,
@@ -30,15 +31,15 @@ def create_parser(argv=None):
     parser.add_argument("--n-linear", "--n_linear", type=int, default=0,
                         help="the number of linear layers")
     parser.add_argument("--n-heads", "--n_heads", type=int, default=1,
-                        help="attention heads of the hidden GAT layers "
-                             "(--model gat; must divide --n-hidden; "
-                             "extension over the reference)")
+                        help="attention heads of the hidden GAT / GATv2 "
+                             "layers (--model gat, gatv2; must divide "
+                             "--n-hidden; extension over the reference)")
     parser.add_argument("--attn-drop", "--attn_drop", type=float,
                         default=0.0,
-                        help="attention dropout of the GAT layers: "
+                        help="attention dropout of the GAT / GATv2 layers: "
                              "probability in [0, 1) of dropping an edge's "
                              "attention coefficient, per head, in training "
-                             "(--model gat)")
+                             "(--model gat, gatv2)")
     parser.add_argument("--norm", choices=["layer", "batch", "none"],
                         default="layer", help="normalization method")
     parser.add_argument("--weight-decay", "--weight_decay", type=float,

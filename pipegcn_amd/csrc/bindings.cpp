@@ -179,5 +179,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "attention-dropout keep bits of explicit (u, v) ids -> bool [n, H]",
         py::arg("u"), py::arg("v"), py::arg("num_heads"), py::arg("seed"),
         py::arg("p"));
+  m.def("gatv2_fwd", &gatv2_fwd_hip,
+        "GATv2 dynamic-attention aggregation over the CSR -> (out, lse)",
+        py::arg("indptr"), py::arg("indices"), py::arg("zl"), py::arg("zr"),
+        py::arg("attn"), py::arg("row_order"), py::arg("num_cols"),
+        py::arg("num_heads"), py::arg("slope"), py::arg("drop_key") = 0,
+        py::arg("drop_thr") = 0, py::arg("drop_scale") = 1.0);
+  m.def("gatv2_bwd_dst", &gatv2_bwd_dst_hip,
+        "GATv2 backward over the CSR -> (d_zr, pa)", py::arg("indptr"),
+        py::arg("indices"), py::arg("g"), py::arg("zl"), py::arg("zr"),
+        py::arg("attn"), py::arg("lse"), py::arg("t"), py::arg("row_order"),
+        py::arg("num_cols"), py::arg("num_heads"), py::arg("slope"),
+        py::arg("drop_key") = 0, py::arg("drop_thr") = 0,
+        py::arg("drop_scale") = 1.0);
+  m.def("gatv2_bwd_src", &gatv2_bwd_src_hip,
+        "GATv2 backward over the CSC -> d_zl", py::arg("indptr"),
+        py::arg("indices"), py::arg("g"), py::arg("zl"), py::arg("zr"),
+        py::arg("attn"), py::arg("lse"), py::arg("t"), py::arg("row_order"),
+        py::arg("num_cols"), py::arg("num_heads"), py::arg("slope"),
+        py::arg("drop_key") = 0, py::arg("drop_thr") = 0,
+        py::arg("drop_scale") = 1.0);
   m.attr("with_hip") = true;
 }

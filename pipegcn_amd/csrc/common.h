@@ -132,6 +132,34 @@ std::vector<torch::Tensor> gat_aggregate_bwd_hip(
 torch::Tensor gat_dropout_keep_hip(torch::Tensor u, torch::Tensor v, int64_t H,
                                    int64_t seed, double p);
 
+// GATv2 (dynamic attention) aggregation (csrc/hip/gatv2.hip):
+//   s_uvh = sum_{f in head h} attn[h,f] * leaky_relu(zl[u,f] + zr[v,f]),
+//   alpha = softmax_u(s), out[v] = sum_u w * alpha * zl[u].
+// Every pass recomputes s from the gathered rows; nothing of size nnz is
+// allocated. zl/zr/g/out/d_zl/d_zr are fp32 or bf16 [nodes, F] with F = H * D
+// and D <= 1024; attn is fp32 [H, D]; lse/t are fp32 [nodes, H]. The drop_*
+// arguments are those of gat_aggregate_fwd_hip (drop_thr == 0: no dropout).
+// -> {out, lse}; rows without edges get 0 and 0.
+std::vector<torch::Tensor> gatv2_fwd_hip(
+    torch::Tensor indptr, torch::Tensor indices, torch::Tensor zl,
+    torch::Tensor zr, torch::Tensor attn, torch::Tensor row_order,
+    int64_t num_cols, int64_t H, double slope, int64_t drop_key,
+    int64_t drop_thr, double drop_scale);
+// Destination-side backward over the CSR, t[v,h] = g[v,h,:] . out[v,h,:].
+// -> {d_zr, pa}: pa is fp32 [num_rows, F] and d_attn is its column sum.
+std::vector<torch::Tensor> gatv2_bwd_dst_hip(
+    torch::Tensor indptr, torch::Tensor indices, torch::Tensor g,
+    torch::Tensor zl, torch::Tensor zr, torch::Tensor attn, torch::Tensor lse,
+    torch::Tensor t, torch::Tensor row_order, int64_t num_cols, int64_t H,
+    double slope, int64_t drop_key, int64_t drop_thr, double drop_scale);
+// Source-side backward; indptr/indices/row_order are the CSC (rows =
+// sources, num_cols = destinations). -> d_zl [num_rows, F].
+torch::Tensor gatv2_bwd_src_hip(
+    torch::Tensor indptr, torch::Tensor indices, torch::Tensor g,
+    torch::Tensor zl, torch::Tensor zr, torch::Tensor attn, torch::Tensor lse,
+    torch::Tensor t, torch::Tensor row_order, int64_t num_cols, int64_t H,
+    double slope, int64_t drop_key, int64_t drop_thr, double drop_scale);
+
 // Fused dual GEMM for the GraphSAGE layer forward:
 //   out[M,N] = x1[M,K] @ w1[N,K]^T + x2[M,K] @ w2[N,K]^T + bias[N]
 // fp32, MFMA (v_mfma_f32_32x32x2_f32). Weights in torch Linear layout [N,K],

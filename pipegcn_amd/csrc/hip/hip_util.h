@@ -1,4 +1,4 @@
-// Pieces shared by the five .hip sources: error checks, the current stream,
+// Pieces shared by the .hip sources: error checks, the current stream,
 // the MFMA 32x32 fp32 accumulator layout and the vector-width dispatch.
 // Each .hip still includes <hip/hip_runtime.h> itself: the build's source
 // translation step writes a *_hip.hip copy of any file that does not name it.

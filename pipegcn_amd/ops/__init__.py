@@ -344,6 +344,178 @@ def gat_aggregate_csr(csr: CSR, z: torch.Tensor, el: torch.Tensor,
                                 False)[1]
 
 
+# widest head the lane layout of csrc/hip/gatv2.hip holds
+GATV2_MAX_HEAD_DIM = 1024
+
+
+def _gatv2_check(csr: CSR, zl, zr, attn, num_heads: int) -> None:
+    """Shape guards shared by both GATv2 paths; raised before any launch."""
+    if num_heads < 1 or zl.dim() != 2 or zl.shape[1] % num_heads != 0:
+        raise ValueError(
+            f"gatv2_aggregate: feature width {tuple(zl.shape)} is not "
+            f"num_heads*D for num_heads={num_heads}")
+    if zr.dim() != 2 or zr.shape[1] != zl.shape[1] or zr.dtype != zl.dtype:
+        raise ValueError(
+            f"gatv2_aggregate: zl/zr must agree in width and dtype, got "
+            f"{tuple(zl.shape)} {zl.dtype} and {tuple(zr.shape)} {zr.dtype}")
+    head_dim = zl.shape[1] // num_heads
+    if tuple(attn.shape) != (num_heads, head_dim):
+        raise ValueError(
+            f"gatv2_aggregate: attn must be [{num_heads}, {head_dim}], got "
+            f"{tuple(attn.shape)}")
+    if zl.shape[0] < csr.num_cols:
+        raise ValueError(
+            f"gatv2_aggregate: zl has {zl.shape[0]} rows but the graph "
+            f"references {csr.num_cols} source nodes (an under-sized tensor "
+            "would be an out-of-bounds GPU gather)")
+    if zr.shape[0] != csr.num_rows:
+        raise ValueError(
+            f"gatv2_aggregate: zr has {zr.shape[0]} rows, the graph has "
+            f"{csr.num_rows} destination nodes")
+    if zl.is_cuda and head_dim > GATV2_MAX_HEAD_DIM:
+        raise ValueError(
+            f"gatv2_aggregate: head width {head_dim} exceeds the kernels' "
+            f"{GATV2_MAX_HEAD_DIM}")
+
+
+def _gatv2_aggregate_torch(csr: CSR, zl, zr, attn, num_heads: int,
+                           slope: float, drop=None):
+    """Dynamic-attention aggregation composed from torch ops under ordinary
+    autograd: the CPU test tier and rank-0 eval. [nnz, H, D] temporaries are
+    fine here; the GPU path never makes them. drop = (key, thr, scale)
+    applies the attention-dropout mask the kernels would draw."""
+    rows = csr.num_rows
+    deg = csr.indptr[1:] - csr.indptr[:-1]
+    v = torch.repeat_interleave(torch.arange(rows, device=zl.device), deg)
+    u = csr.indices.long()
+    zlu = zl.float().view(zl.shape[0], num_heads, -1).index_select(0, u)
+    x = zlu + zr.float().view(rows, num_heads, -1).index_select(0, v)
+    s = (torch.nn.functional.leaky_relu(x, slope) * attn.float()).sum(-1)
+    # the row maximum is a shift only (softmax is invariant to it)
+    m = torch.zeros(rows, num_heads, device=zl.device).scatter_reduce(
+        0, v.unsqueeze(1).expand_as(s), s.detach(), "amax",
+        include_self=False)
+    ex = torch.exp(s - m.index_select(0, v))
+    den = torch.zeros(rows, num_heads, device=zl.device).index_add(0, v, ex)
+    alpha = ex / den.index_select(0, v)
+    if drop is not None:
+        key, thr, scale = drop
+        keep = _gat_keep_hash(u, v, num_heads, key) >= thr
+        alpha = alpha * (keep.to(alpha.dtype) * scale)
+    out = torch.zeros(rows, num_heads, zlu.shape[2], device=zl.device)
+    out = out.index_add(0, v, alpha.unsqueeze(-1) * zlu)
+    return out.view(rows, -1).to(zl.dtype)
+
+
+def _gatv2_forward_hip(csr: CSR, zl, zr, attn, num_heads, slope,
+                       drop=(0, 0, 1.0)):
+    """One gather pass on the gfx950 kernel -> (out, lse). Uses
+    csr.row_order as given. drop = (key, thr, scale); thr 0 is no attention
+    dropout."""
+    ro = csr.row_order if csr.row_order is not None else torch.Tensor()
+    return native().gatv2_fwd(csr.indptr, csr.indices, zl, zr, attn, ro,
+                              csr.num_cols, num_heads, slope, *drop)
+
+
+class _Gatv2Aggregate(torch.autograd.Function):
+    """out[v] = sum_u softmax_u(<a, leaky_relu(zl[u] + zr[v])>) zl[u] per
+    head.
+
+    Saves per-node tensors only (zl, zr, attn, lse, out). The backward is
+    two gather passes that recompute the score per edge: over the CSR for
+    d_zr and the per-node pa (d_attn is its native column sum), over the CSC
+    for d_zl. Attention dropout adds three scalars and no tensor.
+    """
+
+    @staticmethod
+    def forward(ctx, graph: HaloGraph, zl, zr, attn, num_heads, slope, drop):
+        out, lse = _gatv2_forward_hip(graph.csr, zl, zr, attn, num_heads,
+                                      slope, drop)
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(zl, zr, attn, lse, out)
+        ctx.graph, ctx.num_heads, ctx.slope = graph, num_heads, slope
+        ctx.drop = drop
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        zl, zr, attn, lse, out = ctx.saved_tensors
+        csr, csc, H = ctx.graph.csr, ctx.graph.csc, ctx.num_heads
+        g = g.contiguous()
+        n = g.shape[0]
+        # per-node per-head dot: an elementwise pass over [num_in, F]
+        t = (g.view(n, H, -1).float() * out.view(n, H, -1).float()).sum(-1)
+
+        def order(m):
+            return m.row_order if m.row_order is not None else torch.Tensor()
+
+        d_zr, pa = native().gatv2_bwd_dst(
+            csr.indptr, csr.indices, g, zl, zr, attn, lse, t, order(csr),
+            csr.num_cols, H, ctx.slope, *ctx.drop)
+        d_zl = native().gatv2_bwd_src(
+            csc.indptr, csc.indices, g, zl, zr, attn, lse, t, order(csc),
+            csc.num_cols, H, ctx.slope, *ctx.drop)
+        d_attn = native().colsum(pa).view_as(attn)
+        if d_zl.shape[0] < zl.shape[0]:  # rows the graph never references
+            d_zl = torch.cat((d_zl, d_zl.new_zeros(
+                zl.shape[0] - d_zl.shape[0], d_zl.shape[1])))
+        return None, d_zl, d_zr, d_attn, None, None, None
+
+
+def gatv2_aggregate(graph: HaloGraph, zl: torch.Tensor, zr: torch.Tensor,
+                    attn: torch.Tensor, num_heads: int, slope: float = 0.2,
+                    attn_drop: float = 0.0,
+                    seed: Optional[int] = None) -> torch.Tensor:
+    """Differentiable GATv2 (dynamic attention) aggregation over the halo
+    graph.
+
+    zl [num_all, H*D] are the source-side projections of all local nodes, zr
+    [num_in, H*D] the destination-side ones, attn [H, D] the attention
+    vector; the score of edge u -> v and head h is
+    <attn[h], leaky_relu(zl[u,h] + zr[v,h])>, softmaxed over the sources of
+    v. Returns out [num_in, H*D] = sum_u alpha_uv zl[u] (no bias). attn is
+    used in fp32 and its gradient comes back in the incoming dtype. Nothing
+    of size nnz is allocated on the GPU path, forward or backward
+    (docs/DESIGN.md); heads wider than GATV2_MAX_HEAD_DIM are refused there.
+
+    attn_drop and seed are those of `gat_aggregate`: the same endpoint hash
+    (`gat_dropout_keep`), applied after the softmax, recomputed in every
+    pass; attn_drop == 0 draws nothing from the generator.
+    """
+    if not 0.0 <= attn_drop < 1.0:
+        raise ValueError(
+            f"gatv2_aggregate: attn_drop={attn_drop} is outside [0, 1)")
+    _gatv2_check(graph.csr, zl, zr, attn, num_heads)
+    drop = (0, 0, 1.0)
+    if attn_drop > 0.0:
+        if seed is None:
+            # host-drawn, as fused_dropout: no device sync
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        drop = _gat_dropout_params(seed, attn_drop)
+    if not zl.is_cuda:
+        return _gatv2_aggregate_torch(graph.csr, zl, zr, attn, num_heads,
+                                      slope, drop if drop[1] > 0 else None)
+    # the fp32 cast is an autograd node: d_attn returns in attn's dtype
+    return _Gatv2Aggregate.apply(graph, zl.contiguous(), zr.contiguous(),
+                                 attn.float().contiguous(), num_heads, slope,
+                                 drop)
+
+
+def gatv2_aggregate_csr(csr: CSR, zl: torch.Tensor, zr: torch.Tensor,
+                        attn: torch.Tensor, num_heads: int,
+                        slope: float = 0.2) -> torch.Tensor:
+    """Forward-only GATv2 aggregation over a plain CSR (full-graph eval over
+    FullGraph.csr); never drops."""
+    _gatv2_check(csr, zl, zr, attn, num_heads)
+    with torch.no_grad():
+        if not zl.is_cuda:
+            return _gatv2_aggregate_torch(csr, zl, zr, attn, num_heads,
+                                          slope)
+        return _gatv2_forward_hip(csr, zl.contiguous(), zr.contiguous(),
+                                  attn.float().contiguous(), num_heads,
+                                  slope)[0]
+
+
 class _BiasColsum(torch.autograd.Function):
     """x + b with the bias gradient through the native colsum (see
     sage_dual_linear: torch's own reduce is pathological for thin odd N)."""

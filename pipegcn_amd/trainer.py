@@ -188,6 +188,14 @@ def create_model(layer_size, args):
                    train_size=args.n_train,
                    n_heads=getattr(args, "n_heads", 1),
                    attn_drop=getattr(args, "attn_drop", 0.0))
+    if args.model == "gatv2":
+        from pipegcn_amd.models.gatv2 import GATv2
+
+        return GATv2(layer_size, F.relu, args.use_pp, norm=args.norm,
+                     dropout=args.dropout, n_linear=args.n_linear,
+                     train_size=args.n_train,
+                     n_heads=getattr(args, "n_heads", 1),
+                     attn_drop=getattr(args, "attn_drop", 0.0))
     raise NotImplementedError(f"unknown model {args.model}")
 
 

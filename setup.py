@@ -27,6 +27,7 @@ ext = CUDAExtension(
         "pipegcn_amd/csrc/hip/wgrad.hip",
         "pipegcn_amd/csrc/hip/dual_dgrad.hip",
         "pipegcn_amd/csrc/hip/gat.hip",
+        "pipegcn_amd/csrc/hip/gatv2.hip",
     ],
     extra_compile_args={
         # -fopenmp: at::parallel_for is a header template — its OpenMP

@@ -19,9 +19,15 @@ peers it reports launch time only and cannot serve here.
 instances of the two aggregate kernels in the kernel table (row_stats and
 the SpMM columns do not change), and GAT(attn_drop=P) under `--epoch`.
 
+`--v2` adds the GATv2 kernels (csrc/hip/gatv2.hip) under the same protocol,
+in the same rounds: gatv2_fwd, gatv2_bwd_dst (CSR pass), gatv2_bwd_src (CSC
+pass), ops.gatv2_aggregate forward and forward+backward, and GATv2 with 4
+heads under `--epoch`.
+
     python tools/microbench/gat_bench.py [--shape reddit] [--feats 256]
     python tools/microbench/gat_bench.py --epoch
     python tools/microbench/gat_bench.py [--epoch] --attn-drop 0.6
+    python tools/microbench/gat_bench.py [--epoch] --v2
 """
 import argparse
 import json
@@ -47,6 +53,8 @@ ap.add_argument("--epoch", action="store_true",
                 help="time whole training epochs instead of the kernels")
 ap.add_argument("--attn-drop", "--attn_drop", type=float, default=0.0,
                 help="attention dropout of every GAT call (default: none)")
+ap.add_argument("--v2", action="store_true",
+                help="also time the GATv2 kernels / model")
 args = ap.parse_args()
 if not 0.0 <= args.attn_drop < 1.0:
     ap.error("--attn-drop must be in [0, 1)")
@@ -95,6 +103,7 @@ def epoch_bench():
     import torch.nn.functional as Fn
 
     from pipegcn_amd.models.gat import GAT
+    from pipegcn_amd.models.gatv2 import GATv2
     from pipegcn_amd.models.gcn import GCN
     from pipegcn_amd.models.sage import GraphSAGE
     from pipegcn_amd.parallel import context as ctx
@@ -112,11 +121,14 @@ def epoch_bench():
                                dtype=dtype)
         feat = rp.ndata["feat"].to(dtype)
         steps = {}
-        for name, cls, kw, d in (
-                ("graphsage", GraphSAGE, dict(use_pp=False), deg),
-                ("gcn", GCN, {}, deg_all),
-                ("gat-4-heads", GAT,
-                 dict(n_heads=4, attn_drop=args.attn_drop), None)):
+        models = [("graphsage", GraphSAGE, dict(use_pp=False), deg),
+                  ("gcn", GCN, {}, deg_all),
+                  ("gat-4-heads", GAT,
+                   dict(n_heads=4, attn_drop=args.attn_drop), None)]
+        if args.v2:
+            models.append(("gatv2-4-heads", GATv2,
+                           dict(n_heads=4, attn_drop=args.attn_drop), None))
+        for name, cls, kw, d in models:
             torch.manual_seed(0)
             model = cls(layer_size, Fn.relu, dropout=0.5, norm="layer",
                         train_size=part.n_train, **kw).to(dev).to(dtype)
@@ -192,7 +204,7 @@ for dname in args.dtypes:
             zr.grad = None
             ops.spmm_mean(hg, zr, inv).backward(g)
 
-        ms = bench({
+        fns = {
             "row_stats": lambda: nat.gat_row_stats(
                 csr.indptr, csr.indices, el, er, csr.num_cols, SLOPE),
             "agg_fwd": lambda: nat.gat_aggregate_fwd(
@@ -209,12 +221,49 @@ for dname in args.dtypes:
                 hg, z, el, er, H, SLOPE, args.attn_drop, DROP_SEED),
             "spmm_fwd_bwd": spmm_fb,
             "gat_fwd_bwd": gat_fb,
-        })
+        }
+        if args.v2:
+            # zl = z on all rows, zr = a second projection of the dst rows
+            zr2 = torch.randn(rp.num_in, F, device=dev,
+                              generator=gen).to(dtype)
+            attn = torch.randn(H, F // H, device=dev,
+                               generator=gen) / (F // H) ** 0.5
+            out2, lse2 = nat.gatv2_fwd(csr.indptr, csr.indices, z, zr2, attn,
+                                       ro, csr.num_cols, H, SLOPE)
+            t2 = (g.view(-1, H, F // H).float()
+                  * out2.view(-1, H, F // H).float()).sum(-1)
+            zr2r = zr2.clone().requires_grad_(True)
+            attnr = attn.clone().requires_grad_(True)
+
+            def v2_fb():
+                zr.grad = zr2r.grad = attnr.grad = None
+                ops.gatv2_aggregate(hg, zr, zr2r, attnr, H, SLOPE,
+                                    args.attn_drop, DROP_SEED).backward(g)
+
+            fns.update({
+                "v2_fwd_k": lambda: nat.gatv2_fwd(
+                    csr.indptr, csr.indices, z, zr2, attn, ro, csr.num_cols,
+                    H, SLOPE, *drop),
+                "v2_bwd_dst": lambda: nat.gatv2_bwd_dst(
+                    csr.indptr, csr.indices, g, z, zr2, attn, lse2, t2, ro,
+                    csr.num_cols, H, SLOPE, *drop),
+                "v2_bwd_src": lambda: nat.gatv2_bwd_src(
+                    csc.indptr, csc.indices, g, z, zr2, attn, lse2, t2, roc,
+                    csc.num_cols, H, SLOPE, *drop),
+                "v2_fwd": lambda: ops.gatv2_aggregate(
+                    hg, z, zr2, attn, H, SLOPE, args.attn_drop, DROP_SEED),
+                "v2_fwd_bwd": v2_fb,
+            })
+        ms = bench(fns)
         # logical bytes per edge: index + gathered row (+ per-head scalars);
         # the bwd gathers one packed 16 B (er, lse, t, 0) per edge and head
         per_edge = {"row_stats": 4 + 4 * H, "agg_fwd": es * F + 4 * H + 4,
                     "agg_fwd_aux": es * F + 4 * H + 4,
                     "agg_bwd": es * F + 16 * H + 4, "spmm_fwd": es * F + 4}
+        if args.v2:
+            # the CSC pass gathers two rows (g, zr) and 8 B (lse, t) per head
+            per_edge.update({"v2_fwd_k": es * F + 4, "v2_bwd_dst": es * F + 4,
+                             "v2_bwd_src": 2 * es * F + 8 * H + 4})
         rec = dict(dtype=dname, H=H, F=F, nnz=nnz, attn_drop=args.attn_drop,
                    ms={k: round(v, 3) for k, v in ms.items()},
                    tb_per_s={k: round(nnz * b / ms[k] / 1e9, 3)
@@ -222,6 +271,10 @@ for dname in args.dtypes:
                    fwd_ratio=round(ms["gat_fwd"] / ms["spmm_fwd"], 3),
                    fwd_bwd_ratio=round(ms["gat_fwd_bwd"]
                                        / ms["spmm_fwd_bwd"], 3))
+        if args.v2:
+            rec["v2_fwd_ratio"] = round(ms["v2_fwd"] / ms["spmm_fwd"], 3)
+            rec["v2_fwd_bwd_ratio"] = round(ms["v2_fwd_bwd"]
+                                            / ms["spmm_fwd_bwd"], 3)
         print(json.dumps(rec), flush=True)
         rows.append(rec)
         del z, g, el, er, zr, elr, err, out, lse, t
@@ -236,3 +289,16 @@ for r in rows:
           f"{m['agg_bwd']:.2f} | {m['spmm_fwd']:.2f} | {m['gat_fwd']:.2f} | "
           f"{r['fwd_ratio']:.2f} | {m['spmm_fwd_bwd']:.2f} | "
           f"{m['gat_fwd_bwd']:.2f} | {r['fwd_bwd_ratio']:.2f} |")
+
+if args.v2:
+    print("\n| dtype | H | v2 fwd kernel | v2 bwd dst (CSR) | v2 bwd src (CSC)"
+          " | v2 fwd | / spmm | / gat | v2 f+b | / spmm | / gat |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|")
+    for r in rows:
+        m = r["ms"]
+        print(f"| {r['dtype']} | {r['H']} | {m['v2_fwd_k']:.2f} | "
+              f"{m['v2_bwd_dst']:.2f} | {m['v2_bwd_src']:.2f} | "
+              f"{m['v2_fwd']:.2f} | {r['v2_fwd_ratio']:.2f} | "
+              f"{m['v2_fwd'] / m['gat_fwd']:.2f} | {m['v2_fwd_bwd']:.2f} | "
+              f"{r['v2_fwd_bwd_ratio']:.2f} | "
+              f"{m['v2_fwd_bwd'] / m['gat_fwd_bwd']:.2f} |")
