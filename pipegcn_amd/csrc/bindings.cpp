@@ -27,6 +27,26 @@ static torch::Tensor spmm(torch::Tensor indptr, torch::Tensor indices,
   return spmm_cpu(indptr, indices, feat, dst_scale, src_scale, num_rows);
 }
 
+// GPU-only: ops.pack_rows_reference is the torch mirror of the layout
+static torch::Tensor pack_rows(torch::Tensor x) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2, "pack_rows is the GPU path");
+  auto packed = torch::empty({x.size(0), packed_layout(x.size(1)).stride_words},
+                             x.options().dtype(torch::kInt));
+  pack_rows_hip(x, packed);
+  return packed;
+}
+
+static torch::Tensor spmm_packed(torch::Tensor indptr, torch::Tensor indices,
+                                 torch::Tensor packed, int64_t F,
+                                 torch::Tensor dst_scale,
+                                 torch::Tensor row_order, int64_t num_rows) {
+  TORCH_CHECK(packed.is_cuda(), "spmm_packed is the GPU path");
+  auto out = torch::empty({num_rows, F},
+                          packed.options().dtype(torch::kFloat));
+  spmm_packed_hip(indptr, indices, packed, F, dst_scale, row_order, out);
+  return out;
+}
+
 static torch::Tensor gather_rows(torch::Tensor src, torch::Tensor idx) {
   if (src.is_cuda()) {
     auto out = torch::empty({idx.numel(), src.size(1)}, src.options());
@@ -137,6 +157,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("partition_graph", &partition_graph_cpu,
         "BFS-grown + refined k-way partitioner (cut/vol objective)");
   m.def("spmm", &spmm, "CSR SpMM with fused scale epilogue (fwd & transpose)");
+  m.def("pack_rows", &pack_rows,
+        "fp32 [N, F] -> packed rows int32 [N, stride_words]");
+  m.def("spmm_packed", &spmm_packed,
+        "CSR SpMM over packed rows (fp32, dst_scale epilogue)");
   m.def("gather_rows", &gather_rows, "out[i,:] = src[idx[i],:]");
   m.def("gather_rows_out", &gather_rows_out,
         "gather into a preallocated out buffer");

@@ -52,6 +52,27 @@ void spmm_csr_hip(torch::Tensor indptr, torch::Tensor indices,
                   torch::Tensor src_scale, torch::Tensor row_order,
                   torch::Tensor out);
 
+// Packed rows (csrc/hip/spmm_packed.hip): one fixed-stride record per row of a
+// fp32 [N, F] tensor, in 4-byte words: mask_words header entries {uint32 mask,
+// uint32 exclusive prefix count} (one per 32 columns), padding up to hdr_words
+// (a multiple of 4), then the row's non-zero values in column order. Row u
+// starts at word u * stride_words (a multiple of 32).
+struct PackedLayout {
+  int64_t mask_words;
+  int64_t hdr_words;
+  int64_t stride_words;
+};
+PackedLayout packed_layout(int64_t F);
+// packed: int32 [N, stride_words], written for every row of x (fp32 [N, F]);
+// padding and the value slots past a row's non-zero count stay unwritten.
+void pack_rows_hip(torch::Tensor x, torch::Tensor packed);
+// spmm_csr_hip over packed rows (fp32, no src_scale): bitwise the result of
+// the dense kernel on the tensor the rows were packed from. The caller
+// guarantees that every column index is below packed.size(0).
+void spmm_packed_hip(torch::Tensor indptr, torch::Tensor indices,
+                     torch::Tensor packed, int64_t F, torch::Tensor dst_scale,
+                     torch::Tensor row_order, torch::Tensor out);
+
 // out[i,:] = src[idx[i],:]
 void gather_rows_hip(torch::Tensor src, torch::Tensor idx, torch::Tensor out);
 

@@ -89,6 +89,127 @@ def spmm(csr: CSR, feat: torch.Tensor,
                          ro, csr.num_rows)
 
 
+def packed_row_layout(F: int):
+    """(mask_words, hdr_words, stride_words) of a packed row of width F, in
+    4-byte words, as csrc/hip/spmm_packed.hip lays it out (docs/DESIGN.md,
+    "Packed rows"): mask_words header entries {uint32 mask, uint32 exclusive
+    prefix count}, one per 32 columns; padding to hdr_words (a multiple of
+    4, so the values start 16-byte aligned); then the non-zero values in
+    column order. stride_words leaves 8 words of slack after F value slots
+    and is a multiple of 32 (128 B)."""
+    mask_words = (F + 31) // 32
+    hdr_words = (2 * mask_words + 3) // 4 * 4
+    stride_words = (hdr_words + F + 8 + 31) // 32 * 32
+    return mask_words, hdr_words, stride_words
+
+
+def pack_rows_reference(x: torch.Tensor) -> torch.Tensor:
+    """The torch mirror of the device row-packing kernel: fp32 [N, F] ->
+    int32 [N, stride_words]. Runs on x's device (CPU-capable). Header and
+    the leading nnz value slots of each row are what the kernel writes, bit
+    for bit; everything else (which the kernel leaves unwritten) is 0 here.
+    "Non-zero" is v != 0: both zeros are dropped, NaN and +-Inf are kept."""
+    if x.dim() != 2 or x.dtype != torch.float32:
+        raise ValueError("pack_rows_reference: fp32 [N, F] only")
+    N, F = x.shape
+    W, hdr, stride = packed_row_layout(F)
+    nz = x != 0
+    nzp = torch.zeros(N, W * 32, dtype=torch.int64, device=x.device)
+    nzp[:, :F] = nz
+    nzp = nzp.view(N, W, 32)
+    mask = (nzp << torch.arange(32, device=x.device)).sum(-1)
+    cnt = nzp.sum(-1)
+    prefix = cnt.cumsum(-1) - cnt
+    out = torch.zeros(N, stride, dtype=torch.int32, device=x.device)
+    # values >= 2^31 wrap to the int32 with the same bits
+    out[:, 0:2 * W:2] = ((mask + 2 ** 31) % 2 ** 32 - 2 ** 31).int()
+    out[:, 1:2 * W:2] = prefix.int()
+    rank = nz.long().cumsum(-1) - 1
+    rows = torch.arange(N, device=x.device).unsqueeze(1).expand(N, F)
+    out[rows[nz], hdr + rank[nz]] = x.contiguous().view(torch.int32)[nz]
+    return out
+
+
+def unpack_rows_reference(packed: torch.Tensor, F: int) -> torch.Tensor:
+    """Inverse of the packing (dropped entries come back as +0.0): int32
+    [N, stride_words] -> fp32 [N, F]. Reads only the header and the value
+    slots the header points at."""
+    W, hdr, stride = packed_row_layout(F)
+    if packed.dim() != 2 or packed.shape[1] != stride \
+            or packed.dtype != torch.int32:
+        raise ValueError("unpack_rows_reference: not packed rows of width "
+                         f"{F}")
+    N = packed.shape[0]
+    mask = packed[:, 0:2 * W:2].long() & _M32
+    prefix = packed[:, 1:2 * W:2].long()
+    bits = (mask.unsqueeze(-1) >> torch.arange(32, device=packed.device)) & 1
+    rank = prefix.unsqueeze(-1) + bits.cumsum(-1) - bits
+    nz = bits.view(N, W * 32)[:, :F].bool()
+    rank = rank.view(N, W * 32)[:, :F]
+    vals = packed[:, hdr:].gather(1, rank.clamp(max=stride - hdr - 1))
+    return torch.where(nz, vals, torch.zeros_like(vals)).view(torch.float32)
+
+
+def pack_rows(x: torch.Tensor) -> torch.Tensor:
+    """Packed rows of a fp32 [N, F] tensor (device kernel on the GPU, the
+    torch mirror elsewhere)."""
+    if x.is_cuda:
+        return native().pack_rows(x.contiguous())
+    return pack_rows_reference(x)
+
+
+def _spmm_packed_width(F: int) -> bool:
+    """Static routing of the forward SpMM by feature width, read off the
+    `spmm_bench --density` table on the Reddit shape (profiles/README.md,
+    "Packed-row forward SpMM"). Pack pass plus packed gather against the
+    dense kernel, at the one half / one quarter of non-zeros that dropout
+    and dropout after ReLU leave: F=602 29.8 / 25.5 vs 41.2 ms, F=256 10.2 /
+    8.8 vs 15.4, F=128 8.7 / 8.5 vs 9.8, F=64 5.9 / 5.6 vs 7.2. It wins at
+    every measured width, layer 0 included; narrower ones were not measured
+    and stay dense. With nothing to skip it costs 10-14 % (F=602 / F=256)."""
+    return F >= 64
+
+
+def _spmm_packed_route(feat: torch.Tensor) -> bool:
+    """Whether _SpmmMean.forward takes the packed path for this input.
+    PIPEGCN_SPMM_PACKED=0 pins the dense kernel everywhere. No density is
+    counted here: that would need a device sync."""
+    if (not feat.is_cuda or feat.dtype != torch.float32
+            or os.environ.get("PIPEGCN_SPMM_PACKED", "1") == "0"
+            or not _spmm_packed_width(feat.shape[1])):
+        return False
+    # the transient packed buffer: near the memory ceiling (papers100M
+    # sizing) stay dense, as the row-order autotune stays put there
+    free, _ = torch.cuda.mem_get_info(feat.device)
+    need = feat.shape[0] * packed_row_layout(feat.shape[1])[2] * 4
+    return free >= need + (2 << 30)
+
+
+def spmm_packed(csr: CSR, feat: torch.Tensor,
+                scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`spmm(csr, feat, scale)` for fp32 GPU inputs, skipping feat's zeros:
+    feat is packed row by row (header of non-zero bits + the non-zero
+    values), then gathered packed. Bitwise equal to `spmm` on any input;
+    faster when a large share of feat is exactly zero (after dropout and
+    ReLU). The packed buffer is transient."""
+    if feat.shape[0] < csr.num_cols:
+        raise ValueError(
+            f"spmm_packed: feat has {feat.shape[0]} rows but the graph "
+            f"references {csr.num_cols} source nodes (an under-sized feat "
+            "would be an out-of-bounds GPU gather)")
+    if not feat.is_cuda or feat.dtype != torch.float32 or feat.dim() != 2:
+        raise ValueError("spmm_packed: fp32 [N, F] GPU tensors only")
+    s = scale if scale is not None else torch.Tensor()
+    # the dense path's row order: its cached autotune decision for this
+    # (graph, F) if it made one, else the LPT order (no second autotune)
+    ro = csr.row_order if csr.row_order is not None else torch.Tensor()
+    if getattr(csr, "_lpt_choice", {}).get(feat.shape[1]) is False:
+        ro = torch.Tensor()
+    packed = native().pack_rows(feat.contiguous())
+    return native().spmm_packed(csr.indptr, csr.indices, packed,
+                                feat.shape[1], s, ro, csr.num_rows)
+
+
 class _SpmmMean(torch.autograd.Function):
     """ah = D^{-1} A h over the halo graph; backward = A^T D^{-1} g."""
 
@@ -97,6 +218,11 @@ class _SpmmMean(torch.autograd.Function):
                 inv_deg: torch.Tensor):
         ctx.graph = graph
         ctx.save_for_backward(inv_deg)
+        # the forward input is dropout's output (half zeros, three quarters
+        # after a ReLU): gather it packed. The backward's input is a dense
+        # gradient and stays on the dense kernel.
+        if _spmm_packed_route(feat):
+            return spmm_packed(graph.csr, feat, inv_deg)
         return spmm(graph.csr, feat, inv_deg)
 
     @staticmethod

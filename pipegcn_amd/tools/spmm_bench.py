@@ -5,8 +5,14 @@ Interleaved within-process rounds (guide §5.4 rule 24): widths alternate so
 run-to-run variance is correlated. Reports ms and effective (logical) GB/s =
 edges * F * 4 / t.
 
+With --density it instead compares the packed-row forward path with the
+dense kernel on features of which only that share is non-zero (what dropout
+and ReLU leave): dense SpMM, pack pass and packed SpMM alternate in the same
+rounds, and the two outputs must be bitwise equal.
+
 Usage (on a GPU box):
     python -m pipegcn_amd.tools.spmm_bench [--f 602 256] [--rounds 5]
+    python -m pipegcn_amd.tools.spmm_bench --f 256 --density 0.25 0.5 1.0
 """
 import argparse
 import os
@@ -25,6 +31,63 @@ def build(n=232_965, avg_deg=492, seed=0):
     return HaloGraph.from_edges(u, v, n, n).to("cuda"), int(v.numel())
 
 
+def density_table(hg, E, inv, widths, densities, rounds, iters):
+    """Dense SpMM, pack pass and packed SpMM on features with the share
+    `density` of non-zeros, alternating in the same rounds. Prints best ms
+    and physical bytes per edge (dense: the row; packed: header plus the
+    mean non-zero payload), and checks the two outputs bitwise."""
+    from pipegcn_amd import native, ops
+
+    n = hg.num_all
+    csr = hg.csr
+    ro = csr.row_order
+    s = inv
+    print("    F  density |  dense ms  B/edge |  pack ms | packed ms  B/edge"
+          " | packed+pack vs dense")
+    for F in widths:
+        W, _, stride = ops.packed_row_layout(F)
+        for d in densities:
+            g = torch.Generator(device="cuda").manual_seed(F)
+            feat = torch.randn(n, F, device="cuda", generator=g)
+            feat *= torch.rand(n, F, device="cuda", generator=g) < d
+            packed = native().pack_rows(feat)
+            nnz = int((feat != 0).sum())
+
+            def dense():
+                return native().spmm(csr.indptr, csr.indices, feat, s,
+                                     torch.Tensor(), ro, csr.num_rows)
+
+            def pack():
+                return native().pack_rows(feat)
+
+            def gather():
+                return native().spmm_packed(csr.indptr, csr.indices, packed,
+                                            F, s, ro, csr.num_rows)
+
+            assert torch.equal(dense().view(torch.int32),
+                               gather().view(torch.int32)), \
+                f"F={F} density={d}: packed SpMM differs from dense"
+            best = {}
+            for _ in range(rounds):
+                for name, fn in (("dense", dense), ("pack", pack),
+                                 ("packed", gather)):
+                    fn()
+                    torch.cuda.synchronize()
+                    t0 = time.time()
+                    for _ in range(iters):
+                        fn()
+                    torch.cuda.synchronize()
+                    t = (time.time() - t0) / iters * 1e3
+                    best[name] = min(best.get(name, t), t)
+            b_dense = 4 * F
+            b_packed = 8 * W + 4 * nnz / n
+            print(f"{F:5d}  {d:7.2f} | {best['dense']:9.2f}  {b_dense:6d} |"
+                  f" {best['pack']:8.3f} | {best['packed']:9.2f} "
+                  f"{b_packed:7.0f} | "
+                  f"{(best['packed'] + best['pack']) / best['dense']:.3f}x")
+            del feat, packed
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--f", type=int, nargs="+", default=[602, 256])
@@ -33,6 +96,12 @@ def main():
     ap.add_argument("--deg", type=int, default=492)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=3)
+    ap.add_argument("--density", type=float, nargs="+", default=None,
+                    metavar="D",
+                    help="instead of the lane-width A/B: for each F and "
+                         "each share D of non-zero features, time the "
+                         "dense SpMM, the pack pass and the packed SpMM "
+                         "(fp32)")
     args = ap.parse_args()
 
     from pipegcn_amd import ops
@@ -42,6 +111,12 @@ def main():
     deg = hg.csr.row_degrees().to("cuda").clamp(min=1)
     inv = (1.0 / deg).contiguous()
     print(f"graph: {n} nodes, {E} edges")
+    if args.density:
+        if args.dtype != "fp32":
+            raise SystemExit("--density: the packed path is fp32 only")
+        density_table(hg, E, inv, args.f, args.density, args.rounds,
+                      args.iters)
+        return
 
     elem = 2 if args.dtype == "bf16" else 4
     for F in args.f:
