@@ -75,11 +75,15 @@ __global__ void spmm_csr_kernel(const int64_t* __restrict__ indptr,
                                 const int32_t* __restrict__ row_order,
                                 T* __restrict__ out, int64_t num_rows,
                                 int64_t F, int64_t nchunks) {
+  // the wave index in a scalar register: row, edge cursor and node ids are
+  // then wave-uniform for the compiler too (spmm_packed.hip has the convention)
+  const int wave_in_block =
+      __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave);
+  const int64_t waves_per_block = blockDim.x / kWave;
   const int64_t wave_global =
-      (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / kWave;
+      static_cast<int64_t>(blockIdx.x) * waves_per_block + wave_in_block;
   const int lane = threadIdx.x & (kWave - 1);
-  const int64_t nwaves =
-      (static_cast<int64_t>(gridDim.x) * blockDim.x) / kWave;
+  const int64_t nwaves = static_cast<int64_t>(gridDim.x) * waves_per_block;
   const int64_t npairs = num_rows * nchunks;
 
   for (int64_t pair = wave_global; pair < npairs; pair += nwaves) {
@@ -113,8 +117,7 @@ __global__ void spmm_csr_kernel(const int64_t* __restrict__ indptr,
           acc[k] += s * to_f32(feat[u * F + f0 + k]);
       }
       for (; e + 4 <= e_end; e += 4) {
-        const int32x4 uu = __builtin_nontemporal_load(
-            reinterpret_cast<const int32x4*>(indices + e));
+        const int32x4 uu = *reinterpret_cast<const int32x4*>(indices + e);
         const int64_t u0 = uu[0];
         const int64_t u1 = uu[1];
         const int64_t u2 = uu[2];
@@ -176,7 +179,8 @@ void launch_spmm(const int64_t* indptr, const int32_t* indices,
                  const float* src_scale, const int32_t* row_order, T* out,
                  int64_t num_rows, int64_t F, hipStream_t stream) {
   const int64_t nchunks = (F + kWave * VEC - 1) / (kWave * VEC);
-  const int threads = 256;  // 4 waves
+  constexpr int threads = 256;  // 4 whole waves: the kernel keeps the
+  static_assert(threads % kWave == 0);  // wave index in a scalar register
   const int64_t npairs = num_rows * nchunks;
   int64_t blocks = (npairs * kWave + threads - 1) / threads;
   // cap the grid; the grid-stride loop covers the rest

@@ -20,7 +20,11 @@
 // group / tail and the same accumulation expressions per column, so the
 // result is bitwise the dense kernel's at any lane width (a skipped column
 // contributes 0.f where the dense kernel loaded a zero; docs/DESIGN.md has
-// the argument).
+// the argument). What differs from the dense kernel besides the gather: the
+// values a wave shares (row, edge cursor, node ids, record bases) are held in
+// scalar registers and the loaded slots are placed with bit-selects, since
+// the parent of this form was bound by its vector instructions, 98 % VALU
+// busy (profiles/README.md, "Packed gather: wave-uniform index path").
 
 #include "../common.h"
 #include "hip_util.h"
@@ -81,37 +85,56 @@ __global__ void pack_rows_kernel(const float* __restrict__ x,
 // runs past the end of the row needs no guard here.
 // ---------------------------------------------------------------------------
 
-struct PackedRef {
-  const uint32_t* base;  // all records
-  int64_t stride_words;
-  int64_t hdr_words;
+// Wave-uniform convention: a wave owns one (row, chunk), so the row, its edge
+// range, the edge cursor, the node ids and every record's base address are
+// the same in all 64 lanes. They are kept in scalar registers (the wave index
+// goes through readfirstlane, from which the compiler derives the rest), the
+// loops branch on scalar conditions, and a lane adds only its own part: a
+// 32-bit byte offset into the record, so the loads take the scalar-base plus
+// vector-offset form.
+
+// byte address of record u: a 32 x 32 -> 64-bit product (u * stride exceeds
+// 2^32 bytes at papers100M scale)
+__device__ __forceinline__ const char* record(const uint32_t* packed,
+                                              int32_t u,
+                                              uint32_t stride_bytes) {
+  return reinterpret_cast<const char*>(packed) +
+         static_cast<uint64_t>(static_cast<uint32_t>(u)) * stride_bytes;
+}
+
+// what a lane keeps per pair: where its header entry sits in any record,
+// which bit of it is its first column, and where the values start
+struct Lane {
+  uint32_t hdr_off;   // byte offset of the header entry of column f0
+  uint32_t bit;       // f0 & 31
+  uint32_t vals_off;  // byte offset of value slot 0
 };
 
-// where a lane's values sit in one record, and which of its columns are set
+// where a lane's values sit in one record (byte offset), and which of its
+// columns are set
 struct Slot {
-  const float* src;
+  uint32_t off;
   uint32_t m;
 };
 
 // the dependent half: one 8-byte header load, then the address arithmetic
-__device__ __forceinline__ uint2 load_header(const PackedRef& p, int64_t u,
-                                             int64_t f0) {
-  return *reinterpret_cast<const uint2*>(p.base + u * p.stride_words +
-                                         2 * (f0 >> 5));
+__device__ __forceinline__ uint2 load_header(const char* rec,
+                                             uint32_t hdr_off) {
+  return *reinterpret_cast<const uint2*>(rec + hdr_off);
 }
 
-__device__ __forceinline__ Slot locate(const PackedRef& p, int64_t u,
-                                       int64_t f0, uint2 h) {
-  const uint32_t bit = static_cast<uint32_t>(f0) & 31u;
-  const uint32_t rank = h.y + __popc(h.x & ((1u << bit) - 1u));
-  return {reinterpret_cast<const float*>(p.base + u * p.stride_words +
-                                         p.hdr_words) + rank,
-          h.x >> bit};
+// The header offset is the same for every record. Hoisted out of a loop, its
+// widening to 64 bits turns every header load into a 64-bit vector add plus a
+// load from a vector address; passed through this once per iteration, the
+// widening stays next to the loads, which then take scalar base + offset.
+__device__ __forceinline__ uint32_t pinned(uint32_t off) {
+  asm volatile("" : "+v"(off));
+  return off;
 }
 
-__device__ __forceinline__ Slot locate(const PackedRef& p, int64_t u,
-                                       int64_t f0) {
-  return locate(p, u, f0, load_header(p, u, f0));
+__device__ __forceinline__ Slot locate(const Lane& l, uint2 h) {
+  const uint32_t rank = h.y + __popc(h.x & ((1u << l.bit) - 1u));
+  return {l.vals_off + 4u * rank, h.x >> l.bit};
 }
 
 // ONE VEC-wide value load at the rank of the first owned column, issued
@@ -125,35 +148,67 @@ template <int VEC>
 using Vals = float __attribute__((ext_vector_type(VEC)));
 
 template <int VEC>
-__device__ __forceinline__ Vals<VEC> fetch(const Slot& s) {
+__device__ __forceinline__ Vals<VEC> fetch(const char* rec, const Slot& s) {
   Vals<VEC> w;
   // 4-byte aligned only: the target reads unaligned multi-dword loads
-  __builtin_memcpy(&w, s.src, sizeof(float) * VEC);
+  __builtin_memcpy(&w, rec + s.off, sizeof(float) * VEC);
   return w;
 }
 
-// v[k] = column k's value or 0.f; a set column's slot is the number of set
-// bits below it
+// v[k] = column k's value or 0.f. The loaded slots are a queue: column k, if
+// set, takes its head and the queue moves up one. Moves are on the bit
+// patterns, under an all-ones / all-zeros word per column: one bit-field
+// extract, then one bit-select per move, 14 vector instructions per edge at
+// VEC = 4 where compares and selects on the slot number took 27. The extract
+// is spelled as the instruction: written in C++ the compiler turns the masks
+// back into compares and selects (profiles/README.md).
+//
+// This and pinned() above steer the instruction selection of one compiler.
+// To re-check after a toolchain change, compile this file with -O3
+// --offload-arch=gfx950 --offload-device-only -S and count the v_*
+// instructions of the innermost loop of spmm_packed_kernel<4> (the basic
+// block with four global_load_dwordx4 and four global_load_dwordx2): 83,
+// among them 16 v_bfe_i32 and 24 bit-selects (v_bfi_b32 or v_bitop3_b32),
+// the loads in the form "v, v_off, s[base:base+1]", no v_cmp and no
+// v_lshl_add_u64. 134 means the
+// masks were folded into selects again, 89 that the header loads went back
+// to vector addresses; <2> and <1> count 42 and 30.
+template <int K>
+__device__ __forceinline__ uint32_t column_mask(uint32_t m) {
+  uint32_t on;
+  asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(on) : "v"(m), "n"(K));
+  return on;
+}
+
+template <int VEC, int K = 0>
+__device__ __forceinline__ void place_from(uint32_t m, uint32_t (&q)[VEC],
+                                           float (&v)[VEC]) {
+  if constexpr (K < VEC) {
+    const uint32_t on = column_mask<K>(m);
+    v[K] = __uint_as_float(q[0] & on);
+#pragma unroll
+    for (int j = 0; j + 1 < VEC - K; ++j)
+      q[j] = (q[j + 1] & on) | (q[j] & ~on);
+    place_from<VEC, K + 1>(m, q, v);
+  }
+}
+
 template <int VEC>
 __device__ __forceinline__ void place(uint32_t m, const Vals<VEC>& w,
                                       float (&v)[VEC]) {
+  uint32_t q[VEC];
 #pragma unroll
-  for (int k = 0; k < VEC; ++k) {
-    const uint32_t slot = __popc(m & ((1u << k) - 1u));
-    float pick = w[0];
-#pragma unroll
-    for (int j = 1; j <= k; ++j) pick = slot == j ? w[j] : pick;
-    v[k] = ((m >> k) & 1u) ? pick : 0.f;
-  }
+  for (int j = 0; j < VEC; ++j) q[j] = __float_as_uint(w[j]);
+  place_from<VEC>(m, q, v);
 }
 
 // the sums are spmm_csr_kernel's, term for term: keep them so
 template <int VEC>
-__device__ __forceinline__ void add_edge(const PackedRef& p, int64_t u,
-                                         int64_t f0, float (&acc)[VEC]) {
+__device__ __forceinline__ void add_edge(const char* rec, const Lane& l,
+                                         float (&acc)[VEC]) {
   float v[VEC];
-  const Slot s = locate(p, u, f0);
-  place<VEC>(s.m, fetch<VEC>(s), v);
+  const Slot s = locate(l, load_header(rec, l.hdr_off));
+  place<VEC>(s.m, fetch<VEC>(rec, s), v);
 #pragma unroll
   for (int k = 0; k < VEC; ++k) acc[k] += v[k];
 }
@@ -176,7 +231,10 @@ __device__ __forceinline__ void add_group(
 // kernel. The 4-edge groups are software-pipelined: the next group's header
 // loads (and the index load two groups ahead) are issued under the current
 // group's value loads, so a group exposes one memory latency instead of three
-// (8.7 against 11.3 ms at F=256, a quarter non-zero; profiles/README.md).
+// (8.7 against 11.3 ms at F=256, a quarter non-zero, before the index path
+// went scalar; profiles/README.md).
+// The block is whole waves (the host asserts it), so the wave index is
+// uniform; see the convention above for what follows from that.
 template <int VEC>
 __global__ void spmm_packed_kernel(const int64_t* __restrict__ indptr,
                                    const int32_t* __restrict__ indices,
@@ -186,20 +244,26 @@ __global__ void spmm_packed_kernel(const int64_t* __restrict__ indptr,
                                    const int32_t* __restrict__ row_order,
                                    float* __restrict__ out, int64_t num_rows,
                                    int64_t F, int64_t nchunks) {
+  const int wave_in_block =
+      __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave);
+  const int64_t waves_per_block = blockDim.x / kWave;
   const int64_t wave_global =
-      (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / kWave;
+      static_cast<int64_t>(blockIdx.x) * waves_per_block + wave_in_block;
   const int lane = threadIdx.x & (kWave - 1);
-  const int64_t nwaves =
-      (static_cast<int64_t>(gridDim.x) * blockDim.x) / kWave;
+  const int64_t nwaves = static_cast<int64_t>(gridDim.x) * waves_per_block;
   const int64_t npairs = num_rows * nchunks;
-  const PackedRef p{packed, stride_words, hdr_words};
+  const uint32_t stride_bytes = static_cast<uint32_t>(stride_words) * 4u;
 
   for (int64_t pair = wave_global; pair < npairs; pair += nwaves) {
     int64_t r = pair / nchunks;
     const int64_t chunk = pair % nchunks;
     if (row_order) r = row_order[r];
     const int64_t f0 = chunk * (kWave * VEC) + lane * VEC;
+    // lane 0 always passes: the uniform values below come from live lanes
     if (f0 >= F) continue;
+    const Lane l{static_cast<uint32_t>(f0 >> 5) * 8u,
+                 static_cast<uint32_t>(f0) & 31u,
+                 static_cast<uint32_t>(hdr_words) * 4u};
 
     float acc[VEC];
 #pragma unroll
@@ -209,48 +273,68 @@ __global__ void spmm_packed_kernel(const int64_t* __restrict__ indptr,
     const int64_t e_end = indptr[r + 1];
     int64_t e = e_begin;
 
-    for (; e < e_end && (e & 3); ++e) add_edge<VEC>(p, indices[e], f0, acc);
-    if (e + 4 <= e_end) {
-      const int32x4 uu = __builtin_nontemporal_load(
-          reinterpret_cast<const int32x4*>(indices + e));
-      Slot s0 = locate(p, uu[0], f0);
-      Slot s1 = locate(p, uu[1], f0);
-      Slot s2 = locate(p, uu[2], f0);
-      Slot s3 = locate(p, uu[3], f0);
+    // The trip counts are unsigned and only tested for (in)equality or in 32
+    // bits: that is what the scalar unit compares (a 64-bit "less than" would
+    // go to the vector unit). peel: the edges before the next multiple of 4,
+    // or the whole row if it ends sooner.
+    const uint64_t deg = static_cast<uint64_t>(e_end - e_begin);
+    uint32_t peel = static_cast<uint32_t>(-e_begin) & 3u;
+    if ((deg >> 2) == 0 && static_cast<uint32_t>(deg) < peel)
+      peel = static_cast<uint32_t>(deg);
+    for (uint32_t i = 0; i != peel; ++i, ++e)
+      add_edge<VEC>(record(packed, indices[e], stride_bytes), l, acc);
+    // whole groups left, this one included
+    uint64_t g = static_cast<uint64_t>(e_end - e) >> 2;
+    if (g != 0) {
+      const int32x4 uu = *reinterpret_cast<const int32x4*>(indices + e);
+      const char* r0 = record(packed, uu[0], stride_bytes);
+      const char* r1 = record(packed, uu[1], stride_bytes);
+      const char* r2 = record(packed, uu[2], stride_bytes);
+      const char* r3 = record(packed, uu[3], stride_bytes);
+      Slot s0 = locate(l, load_header(r0, l.hdr_off));
+      Slot s1 = locate(l, load_header(r1, l.hdr_off));
+      Slot s2 = locate(l, load_header(r2, l.hdr_off));
+      Slot s3 = locate(l, load_header(r3, l.hdr_off));
       // indices of the group after this one (this one again if it is the
       // last: the address stays inside the row)
-      int32x4 un = __builtin_nontemporal_load(reinterpret_cast<const int32x4*>(
-          indices + (e + 8 <= e_end ? e + 4 : e)));
-      while (e + 8 <= e_end) {
-        const int32x4 un2 =
-            __builtin_nontemporal_load(reinterpret_cast<const int32x4*>(
-                indices + (e + 12 <= e_end ? e + 8 : e)));
-        const Vals<VEC> w0 = fetch<VEC>(s0);
-        const Vals<VEC> w1 = fetch<VEC>(s1);
-        const Vals<VEC> w2 = fetch<VEC>(s2);
-        const Vals<VEC> w3 = fetch<VEC>(s3);
-        const uint2 h0 = load_header(p, un[0], f0);
-        const uint2 h1 = load_header(p, un[1], f0);
-        const uint2 h2 = load_header(p, un[2], f0);
-        const uint2 h3 = load_header(p, un[3], f0);
+      int32x4 un = *reinterpret_cast<const int32x4*>(
+          indices + (g != 1 ? e + 4 : e));
+      for (; g != 1; --g) {
+        const int32x4 un2 = *reinterpret_cast<const int32x4*>(
+            indices + (g != 2 ? e + 8 : e));
+        const Vals<VEC> w0 = fetch<VEC>(r0, s0);
+        const Vals<VEC> w1 = fetch<VEC>(r1, s1);
+        const Vals<VEC> w2 = fetch<VEC>(r2, s2);
+        const Vals<VEC> w3 = fetch<VEC>(r3, s3);
+        r0 = record(packed, un[0], stride_bytes);
+        r1 = record(packed, un[1], stride_bytes);
+        r2 = record(packed, un[2], stride_bytes);
+        r3 = record(packed, un[3], stride_bytes);
+        const uint32_t ho = pinned(l.hdr_off);
+        const uint2 h0 = load_header(r0, ho);
+        const uint2 h1 = load_header(r1, ho);
+        const uint2 h2 = load_header(r2, ho);
+        const uint2 h3 = load_header(r3, ho);
         // keep the header loads above the wait for the values
         __builtin_amdgcn_sched_barrier(0);
         add_group<VEC>(s0.m, s1.m, s2.m, s3.m, w0, w1, w2, w3, acc);
-        s0 = locate(p, un[0], f0, h0);
-        s1 = locate(p, un[1], f0, h1);
-        s2 = locate(p, un[2], f0, h2);
-        s3 = locate(p, un[3], f0, h3);
+        s0 = locate(l, h0);
+        s1 = locate(l, h1);
+        s2 = locate(l, h2);
+        s3 = locate(l, h3);
         un = un2;
         e += 4;
       }
-      const Vals<VEC> w0 = fetch<VEC>(s0);
-      const Vals<VEC> w1 = fetch<VEC>(s1);
-      const Vals<VEC> w2 = fetch<VEC>(s2);
-      const Vals<VEC> w3 = fetch<VEC>(s3);
+      const Vals<VEC> w0 = fetch<VEC>(r0, s0);
+      const Vals<VEC> w1 = fetch<VEC>(r1, s1);
+      const Vals<VEC> w2 = fetch<VEC>(r2, s2);
+      const Vals<VEC> w3 = fetch<VEC>(r3, s3);
       add_group<VEC>(s0.m, s1.m, s2.m, s3.m, w0, w1, w2, w3, acc);
       e += 4;
     }
-    for (; e < e_end; ++e) add_edge<VEC>(p, indices[e], f0, acc);
+    const uint32_t tail = static_cast<uint32_t>(e_end - e) & 3u;
+    for (uint32_t i = 0; i != tail; ++i, ++e)
+      add_edge<VEC>(record(packed, indices[e], stride_bytes), l, acc);
 
     const float s = dst_scale ? dst_scale[r] : 1.f;
     if (f0 + VEC <= F) {
@@ -336,15 +420,17 @@ void spmm_packed_hip(torch::Tensor indptr, torch::Tensor indices,
   // lane width: the narrowest that covers the row in one chunk, at most 4.
   // Unlike the dense kernel's, it need not divide F (values are read
   // unaligned, and columns past F read as zero), and wider is faster here:
-  // the gather is bound by (row, chunk) visits, not bytes. At F=256, a
-  // quarter non-zero: 4 -> 8.7 ms, 2 -> 16.0 ms, dense 15.4 ms; 8 loses to
-  // its own selects (18.7 ms) (profiles/README.md).
+  // the cost is per (row, chunk) visit of a wave, not per byte. At F=256, a
+  // quarter non-zero, with the index math still per lane: 4 -> 8.7 ms, 2 ->
+  // 16.0 ms, dense 15.4 ms, 8 lost to its own selects (18.7 ms); 4 is at
+  // 6.7 ms now (profiles/README.md).
   const int vec = F > 128 ? 4 : (F > 64 ? 2 : 1);
   dispatch_vec(vec, [&](auto v) {
     constexpr int VEC = v.value;
     if constexpr (VEC <= 4) {
       const int64_t nchunks = (F + kWave * VEC - 1) / (kWave * VEC);
-      const int threads = 256;  // 4 waves
+      constexpr int threads = 256;  // 4 whole waves: the kernel keeps the
+      static_assert(threads % kWave == 0);  // wave index in a scalar register
       const int64_t npairs = num_rows * nchunks;
       int64_t blocks = (npairs * kWave + threads - 1) / threads;
       blocks = std::min<int64_t>(blocks, 8 * 65536);

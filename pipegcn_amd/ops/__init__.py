@@ -163,10 +163,11 @@ def _spmm_packed_width(F: int) -> bool:
     `spmm_bench --density` table on the Reddit shape (profiles/README.md,
     "Packed-row forward SpMM"). Pack pass plus packed gather against the
     dense kernel, at the one half / one quarter of non-zeros that dropout
-    and dropout after ReLU leave: F=602 29.8 / 25.5 vs 41.2 ms, F=256 10.2 /
-    8.8 vs 15.4, F=128 8.7 / 8.5 vs 9.8, F=64 5.9 / 5.6 vs 7.2. It wins at
+    and dropout after ReLU leave: F=602 27.0 / 20.4 vs 41.3 ms, F=256 9.7 /
+    6.8 vs 15.5, F=128 6.5 / 6.3 vs 9.9, F=64 5.4 / 5.3 vs 7.2. It wins at
     every measured width, layer 0 included; narrower ones were not measured
-    and stay dense. With nothing to skip it costs 10-14 % (F=602 / F=256)."""
+    and stay dense. With nothing to skip it costs 7-13 % (F=602 / F=256)
+    and saves 3-6 % at F=128 / F=64."""
     return F >= 64
 
 
