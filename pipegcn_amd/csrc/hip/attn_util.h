@@ -1,8 +1,12 @@
-// Device helpers shared by the attention aggregation kernels (gat.hip,
-// gatv2.hip): typed vector loads/stores, LeakyReLU, the attention-dropout
-// hash and the fixed-order wave reductions. Everything is force-inlined, so
-// each .hip gets exactly the code it had when these lived in its own
-// anonymous namespace.
+// Shared by the attention aggregation kernels (gat.hip, gatv2.hip).
+// Device side: typed vector loads/stores, LeakyReLU, the attention-dropout
+// hash, the fixed-order wave reduction, the wave-per-pair preamble (wave_ids)
+// and the walk over one row's edges (for_edges). Everything there is
+// force-inlined, so each .hip gets exactly the code it had when these lived
+// in its own anonymous namespace. Host side: the checks that keep an
+// under-sized tensor from becoming an out-of-bounds gather; each takes the
+// op's name for its messages. kWave, int32x4, to_f32, grid_for and
+// aligned_to come from hip_util.h.
 #pragma once
 
 #include "hip_util.h"
@@ -10,20 +14,13 @@
 #include <hip/hip_bf16.h>
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cstdint>
+#include <type_traits>
 
 namespace attn_util {
 
-constexpr int kWave = 64;
-
-using int32x4 = __attribute__((ext_vector_type(4))) int;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
-__device__ __forceinline__ float to_f32(float v) { return v; }
-__device__ __forceinline__ float to_f32(__hip_bfloat16 v) {
-  return __bfloat162float(v);
-}
 template <typename T>
 __device__ __forceinline__ T from_f32(float v);
 template <>
@@ -120,16 +117,128 @@ __device__ __forceinline__ float wave_sum(float x) {
   return x;
 }
 
-// host side: launch geometry and alignment of the wave-per-row kernels
-inline int64_t grid_for(int64_t nwaves, int threads) {
-  int64_t blocks = (nwaves * kWave + threads - 1) / threads;
-  // cap the grid; the grid-stride loops cover the rest
-  blocks = std::min<int64_t>(blocks, 8 * 65536);
-  return blocks == 0 ? 1 : blocks;
+// The wave of a (row, chunk) or (row, head group) pair loop: a kernel walks
+// pairs wave_global, wave_global + nwaves, ... The one place where the
+// scalar-register wave index of spmm_csr_kernel would go (docs/ROADMAP.md).
+struct WaveIds {
+  int64_t wave_global;
+  int lane;
+  int64_t nwaves;
+};
+
+// Called as wave_ids(). The launch geometry arrives through default
+// arguments because those are evaluated in the calling kernel: read inside a
+// device function, blockDim loses the kernel's uniform-block-size guarantee
+// and costs a dependent load at every wave's start.
+__device__ __forceinline__ WaveIds wave_ids(unsigned block = blockIdx.x,
+                                            unsigned block_dim = blockDim.x,
+                                            unsigned thread = threadIdx.x,
+                                            unsigned grid_dim = gridDim.x) {
+  return {(static_cast<int64_t>(block) * block_dim + thread) / kWave,
+          static_cast<int>(thread & (kWave - 1)),
+          (static_cast<int64_t>(grid_dim) * block_dim) / kWave};
 }
 
-inline bool aligned_to(const void* p, int64_t bytes) {
-  return reinterpret_cast<uintptr_t>(p) % bytes == 0;
+// Walk the edges [e, e_end) of one row: peel until e is 4-aligned, then read
+// four indices with one dwordx4 and hand them on U at a time (U gathers in
+// flight), then the tail one by one. fn(integral_constant<int, N>, ids).
+template <int U, typename Fn>
+__device__ __forceinline__ void for_edges(const int32_t* __restrict__ indices,
+                                          int64_t e, int64_t e_end, Fn&& fn) {
+  for (; e < e_end && (e & 3); ++e) {
+    const int32_t one[1] = {indices[e]};
+    fn(std::integral_constant<int, 1>{}, one);
+  }
+  for (; e + 4 <= e_end; e += 4) {
+    const int32x4 q = __builtin_nontemporal_load(
+        reinterpret_cast<const int32x4*>(indices + e));
+    const int32_t ids[4] = {q[0], q[1], q[2], q[3]};
+#pragma unroll
+    for (int b = 0; b < 4; b += U) {
+      int32_t part[U];
+#pragma unroll
+      for (int i = 0; i < U; ++i) part[i] = ids[b + i];
+      fn(std::integral_constant<int, U>{}, part);
+    }
+  }
+  for (; e < e_end; ++e) {
+    const int32_t one[1] = {indices[e]};
+    fn(std::integral_constant<int, 1>{}, one);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// host side: `op` ("gat" / "gatv2") prefixes every message
+// ---------------------------------------------------------------------------
+
+// the attention dropout's folded key, keep threshold and 1 / (1 - p).
+// thr == 0 keeps every edge.
+struct DropArgs {
+  uint32_t key;
+  uint32_t thr;
+  float scale;
+};
+
+inline DropArgs drop_args(const char* op, int64_t key, int64_t thr,
+                          double scale) {
+  TORCH_CHECK(key >= 0 && key <= 0xFFFFFFFFll && thr >= 0 &&
+                  thr <= 0xFFFFFFFFll,
+              op, ": drop_key and drop_thr are 32-bit values");
+  return {static_cast<uint32_t>(key), static_cast<uint32_t>(thr),
+          static_cast<float>(scale)};
+}
+
+inline const int32_t* row_order_ptr(const char* op,
+                                    const torch::Tensor& row_order,
+                                    int64_t num_rows) {
+  if (!row_order.defined() || row_order.numel() == 0) return nullptr;
+  TORCH_CHECK(row_order.is_cuda() && row_order.is_contiguous() &&
+                  row_order.numel() == num_rows &&
+                  row_order.scalar_type() == torch::kInt,
+              op, ": row_order must be a contiguous int32[num_rows]");
+  return row_order.data_ptr<int32_t>();
+}
+
+inline void check_graph(const char* op, const torch::Tensor& indptr,
+                        const torch::Tensor& indices) {
+  TORCH_CHECK(indptr.is_cuda() && indices.is_cuda(), op,
+              ": graph tensors must be on the device");
+  TORCH_CHECK(indptr.scalar_type() == torch::kLong &&
+                  indices.scalar_type() == torch::kInt,
+              op, ": indptr int64 / indices int32");
+  TORCH_CHECK(indptr.is_contiguous() && indices.is_contiguous() &&
+                  indptr.numel() >= 1,
+              op, ": graph tensors must be contiguous");
+  // for_edges reads indices four at a time with one dwordx4
+  TORCH_CHECK(aligned_to(indices.data_ptr(), 16), op,
+              ": indices must be 16-byte aligned");
+}
+
+// a per-node per-head fp32 table with at least `rows` rows
+inline void check_node_table(const char* op, const torch::Tensor& x,
+                             int64_t rows, int64_t H, const char* name) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous() &&
+                  x.scalar_type() == torch::kFloat,
+              op, ": ", name, " must be a contiguous fp32 [nodes, H] tensor");
+  TORCH_CHECK(x.size(1) == H, op, ": ", name, " has ", x.size(1),
+              " heads, expected ", H);
+  TORCH_CHECK(x.size(0) >= rows, op, ": ", name, " has ", x.size(0),
+              " rows but the graph references ", rows);
+}
+
+// a [nodes, F] feature tensor (fp32 or bf16) with at least `rows` rows
+inline void check_features(const char* op, const torch::Tensor& x,
+                           int64_t rows, int64_t H, const char* name) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous(), op, ": ",
+              name, " must be a contiguous [nodes, F] tensor");
+  TORCH_CHECK(x.scalar_type() == torch::kFloat ||
+                  x.scalar_type() == torch::kBFloat16,
+              op, ": ", name, " must be fp32 or bf16");
+  TORCH_CHECK(H >= 1 && x.size(1) >= H && x.size(1) % H == 0, op, ": ", name,
+              " width F=", x.size(1), " is not H*D for H=", H);
+  TORCH_CHECK(x.size(0) >= rows, op, ": ", name, " has ", x.size(0),
+              " rows but the graph references ", rows,
+              " (an under-sized tensor would be an out-of-bounds gather)");
 }
 
 }  // namespace attn_util

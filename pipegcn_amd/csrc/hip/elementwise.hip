@@ -26,10 +26,7 @@
 
 namespace {
 
-__device__ inline float to_f32(float v) { return v; }
-__device__ inline float to_f32(__hip_bfloat16 v) {
-  return __bfloat162float(v);
-}
+// to_f32 is hip_util.h's
 __device__ inline void from_f32(float v, float* p) { *p = v; }
 __device__ inline void from_f32(float v, __hip_bfloat16* p) {
   *p = __float2bfloat16(v);

@@ -37,6 +37,14 @@
 // divides D), so its edge weight is one scalar. Each row's edges are walked
 // in CSR order by one wave: results are bitwise reproducible and independent
 // of row_order.
+//
+// Both aggregate kernels spell the edge walk out (one_edge plus the 4-way
+// body) where gatv2.hip passes one generic lambda to for_edges. Ported to
+// that form the forward spills in two instances and the backward's two
+// 1-element dropout instances fuse other products of the 4-edge sums into
+// FMAs, a last-bit change of dz and d_el (profiles/README.md, "Shared
+// attention scaffolding"). Keep one_edge and the unrolled body in step: same
+// weights, csum / ct from the unmasked c, masking after that.
 
 #include "../common.h"
 #include "attn_util.h"
@@ -52,8 +60,8 @@
 
 namespace {
 
-// ld_vec / st_vec, leaky, the drop_* hash and wave_sum are shared with
-// gatv2.hip
+// ld_vec / st_vec, leaky, the drop_* hash, wave_sum, wave_ids and the
+// host-side input checks are shared with gatv2.hip
 using namespace attn_util;
 
 // heads handled per sweep over a row's edges in gat_row_stats
@@ -104,13 +112,10 @@ __global__ void gat_row_stats_kernel(const int64_t* __restrict__ indptr,
                                      float* __restrict__ lse,
                                      int64_t num_rows, int64_t H,
                                      float slope) {
-  const int64_t wave_global =
-      (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / kWave;
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t nwaves =
-      (static_cast<int64_t>(gridDim.x) * blockDim.x) / kWave;
+  const WaveIds wv = wave_ids();
+  const int lane = wv.lane;
 
-  for (int64_t r = wave_global; r < num_rows; r += nwaves) {
+  for (int64_t r = wv.wave_global; r < num_rows; r += wv.nwaves) {
     const int64_t e_begin = indptr[r];
     const int64_t e_end = indptr[r + 1];
     for (int64_t h0 = 0; h0 < H; h0 += kHeadBlk) {
@@ -172,14 +177,11 @@ gat_aggregate_fwd_kernel(
     T* __restrict__ zc, float* __restrict__ csum, int64_t num_rows, int64_t F,
     int64_t H, int64_t D, int64_t nchunks, float slope, uint32_t key,
     uint32_t thr, float scale) {
-  const int64_t wave_global =
-      (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / kWave;
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t nwaves =
-      (static_cast<int64_t>(gridDim.x) * blockDim.x) / kWave;
+  const WaveIds wv = wave_ids();
+  const int lane = wv.lane;
   const int64_t npairs = num_rows * nchunks;
 
-  for (int64_t pair = wave_global; pair < npairs; pair += nwaves) {
+  for (int64_t pair = wv.wave_global; pair < npairs; pair += wv.nwaves) {
     int64_t r = pair / nchunks;
     const int64_t chunk = pair % nchunks;
     if (row_order) r = row_order[r];
@@ -296,14 +298,11 @@ gat_aggregate_bwd_kernel(
     float* __restrict__ d_el_part, int64_t num_rows, int64_t F, int64_t H,
     int64_t D, int64_t nchunks, float slope, uint32_t key, uint32_t thr,
     float scale) {
-  const int64_t wave_global =
-      (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / kWave;
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t nwaves =
-      (static_cast<int64_t>(gridDim.x) * blockDim.x) / kWave;
+  const WaveIds wv = wave_ids();
+  const int lane = wv.lane;
   const int64_t npairs = num_rows * nchunks;
 
-  for (int64_t pair = wave_global; pair < npairs; pair += nwaves) {
+  for (int64_t pair = wv.wave_global; pair < npairs; pair += wv.nwaves) {
     int64_t r = pair / nchunks;
     const int64_t chunk = pair % nchunks;
     if (row_order) r = row_order[r];
@@ -430,22 +429,6 @@ template <typename T, bool AUX, bool DROP>
 constexpr int kFwdMaxVec = (AUX && sizeof(T) == 2) ? 4 : 16 / sizeof(T);
 constexpr int kBwdMaxVec = 4;
 
-// host side of the attention dropout: the folded key, the keep threshold and
-// 1 / (1 - p). thr == 0 keeps every edge and runs the DROP = false instances.
-struct DropArgs {
-  uint32_t key;
-  uint32_t thr;
-  float scale;
-};
-
-DropArgs drop_args(int64_t key, int64_t thr, double scale) {
-  TORCH_CHECK(key >= 0 && key <= 0xFFFFFFFFll && thr >= 0 &&
-                  thr <= 0xFFFFFFFFll,
-              "gat: drop_key and drop_thr are 32-bit values");
-  return {static_cast<uint32_t>(key), static_cast<uint32_t>(thr),
-          static_cast<float>(scale)};
-}
-
 // low word of splitmix64(seed): the 32-bit key of one call's masks
 uint32_t drop_fold_seed(int64_t seed) {
   uint64_t x = static_cast<uint64_t>(seed) + 0x9E3779B97F4A7C15ull;
@@ -477,69 +460,21 @@ int gat_pick_vec(int64_t D, int64_t elem_size, int max_vec,
   return 1;
 }
 
-const int32_t* row_order_ptr(const torch::Tensor& row_order,
-                             int64_t num_rows) {
-  if (!row_order.defined() || row_order.numel() == 0) return nullptr;
-  TORCH_CHECK(row_order.is_cuda() && row_order.is_contiguous() &&
-                  row_order.numel() == num_rows &&
-                  row_order.scalar_type() == torch::kInt,
-              "gat: row_order must be a contiguous int32[num_rows]");
-  return row_order.data_ptr<int32_t>();
-}
-
-void check_graph(const torch::Tensor& indptr, const torch::Tensor& indices) {
-  TORCH_CHECK(indptr.is_cuda() && indices.is_cuda(),
-              "gat: graph tensors must be on the device");
-  TORCH_CHECK(indptr.scalar_type() == torch::kLong &&
-                  indices.scalar_type() == torch::kInt,
-              "gat: indptr int64 / indices int32");
-  TORCH_CHECK(indptr.is_contiguous() && indices.is_contiguous() &&
-                  indptr.numel() >= 1,
-              "gat: graph tensors must be contiguous");
-  // the unrolled edge loop reads indices four at a time with one dwordx4
-  TORCH_CHECK(aligned_to(indices.data_ptr(), 16),
-              "gat: indices must be 16-byte aligned");
-}
-
-// a per-node per-head fp32 table with at least `rows` rows
-void check_node_table(const torch::Tensor& x, int64_t rows, int64_t H,
-                      const char* name) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous() &&
-                  x.scalar_type() == torch::kFloat,
-              "gat: ", name, " must be a contiguous fp32 [nodes, H] tensor");
-  TORCH_CHECK(x.size(1) == H, "gat: ", name, " has ", x.size(1),
-              " heads, expected ", H);
-  TORCH_CHECK(x.size(0) >= rows, "gat: ", name, " has ", x.size(0),
-              " rows but the graph references ", rows);
-}
-
-// a [nodes, F] feature tensor (fp32 or bf16) with at least `rows` rows
-void check_features(const torch::Tensor& x, int64_t rows, int64_t H,
-                    const char* name) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous(),
-              "gat: ", name, " must be a contiguous [nodes, F] tensor");
-  TORCH_CHECK(x.scalar_type() == torch::kFloat ||
-                  x.scalar_type() == torch::kBFloat16,
-              "gat: ", name, " must be fp32 or bf16");
-  TORCH_CHECK(H >= 1 && x.size(1) >= H && x.size(1) % H == 0, "gat: ", name,
-              " width F=", x.size(1), " is not H*D for H=", H);
-  TORCH_CHECK(x.size(0) >= rows, "gat: ", name, " has ", x.size(0),
-              " rows but the graph references ", rows,
-              " (an under-sized tensor would be an out-of-bounds gather)");
-}
+// the shared host checks (attn_util.h), with this op's name in the messages
+constexpr const char* kOp = "gat";
 
 }  // namespace
 
 torch::Tensor gat_row_stats_hip(torch::Tensor indptr, torch::Tensor indices,
                                 torch::Tensor el, torch::Tensor er,
                                 int64_t num_cols, double slope) {
-  check_graph(indptr, indices);
+  check_graph(kOp, indptr, indices);
   const int64_t num_rows = indptr.numel() - 1;
   TORCH_CHECK(er.dim() == 2, "gat: er must be [num_rows, H]");
   const int64_t H = er.size(1);
   TORCH_CHECK(H >= 1, "gat: at least one head");
-  check_node_table(er, num_rows, H, "er");
-  check_node_table(el, num_cols, H, "el");
+  check_node_table(kOp, er, num_rows, H, "er");
+  check_node_table(kOp, el, num_cols, H, "el");
   auto lse = torch::empty({num_rows, H}, er.options());
   const int threads = 256;
   hipLaunchKernelGGL(gat_row_stats_kernel, dim3(grid_for(num_rows, threads)),
@@ -604,15 +539,15 @@ std::vector<torch::Tensor> gat_aggregate_fwd_hip(
     torch::Tensor el, torch::Tensor er, torch::Tensor lse,
     torch::Tensor row_order, int64_t num_cols, int64_t H, double slope,
     bool with_aux, int64_t drop_key, int64_t drop_thr, double drop_scale) {
-  check_graph(indptr, indices);
-  const DropArgs drop = drop_args(drop_key, drop_thr, drop_scale);
+  check_graph(kOp, indptr, indices);
+  const DropArgs drop = drop_args(kOp, drop_key, drop_thr, drop_scale);
   const int64_t num_rows = indptr.numel() - 1;
-  check_features(z, num_cols, H, "z");
+  check_features(kOp, z, num_cols, H, "z");
   const int64_t F = z.size(1);
-  check_node_table(el, num_cols, H, "el");
-  check_node_table(er, num_rows, H, "er");
-  check_node_table(lse, num_rows, H, "lse");
-  const int32_t* rop = row_order_ptr(row_order, num_rows);
+  check_node_table(kOp, el, num_cols, H, "el");
+  check_node_table(kOp, er, num_rows, H, "er");
+  check_node_table(kOp, lse, num_rows, H, "lse");
+  const int32_t* rop = row_order_ptr(kOp, row_order, num_rows);
   auto out = torch::empty({num_rows, F}, z.options());
   torch::Tensor zc, csum;
   if (with_aux) {
@@ -678,19 +613,19 @@ std::vector<torch::Tensor> gat_aggregate_bwd_hip(
     torch::Tensor t, torch::Tensor row_order, int64_t num_cols, int64_t H,
     double slope, int64_t drop_key, int64_t drop_thr, double drop_scale) {
   // indptr/indices are the CSC: rows = source nodes, columns = destinations
-  check_graph(indptr, indices);
-  const DropArgs drop = drop_args(drop_key, drop_thr, drop_scale);
+  check_graph(kOp, indptr, indices);
+  const DropArgs drop = drop_args(kOp, drop_key, drop_thr, drop_scale);
   const int64_t num_rows = indptr.numel() - 1;
-  check_features(g, num_cols, H, "g");
-  check_features(z, num_rows, H, "z");
+  check_features(kOp, g, num_cols, H, "g");
+  check_features(kOp, z, num_rows, H, "z");
   const int64_t F = z.size(1);
   TORCH_CHECK(g.size(1) == F && g.scalar_type() == z.scalar_type(),
               "gat: g and z must agree in width and dtype");
-  check_node_table(el, num_rows, H, "el");
-  check_node_table(er, num_cols, H, "er");
-  check_node_table(lse, num_cols, H, "lse");
-  check_node_table(t, num_cols, H, "t");
-  const int32_t* rop = row_order_ptr(row_order, num_rows);
+  check_node_table(kOp, el, num_rows, H, "el");
+  check_node_table(kOp, er, num_cols, H, "er");
+  check_node_table(kOp, lse, num_cols, H, "lse");
+  check_node_table(kOp, t, num_cols, H, "t");
+  const int32_t* rop = row_order_ptr(kOp, row_order, num_rows);
   auto dz = torch::empty({num_rows, F}, z.options());
   // (er, lse, t, 0) per destination and head — node-sized, 16-byte aligned
   auto dst_state =

@@ -59,6 +59,8 @@
 
 namespace {
 
+// ld_vec / st_vec, leaky, the drop_* hash, wave_ids, for_edges and the
+// host-side input checks are shared with gat.hip
 using namespace attn_util;
 
 // finite stand-in for -inf: exp(kNegBig - s) is 0, not NaN
@@ -187,34 +189,6 @@ __device__ __forceinline__ void st_row(T* row,
   }
 }
 
-// Walk the edges [e, e_end) of one row: peel until e is 4-aligned, then read
-// four indices with one dwordx4 and hand them on U at a time (U gathers in
-// flight), then the tail one by one. fn(integral_constant<int, N>, ids).
-template <int U, typename Fn>
-__device__ __forceinline__ void for_edges(const int32_t* __restrict__ indices,
-                                          int64_t e, int64_t e_end, Fn&& fn) {
-  for (; e < e_end && (e & 3); ++e) {
-    const int32_t one[1] = {indices[e]};
-    fn(std::integral_constant<int, 1>{}, one);
-  }
-  for (; e + 4 <= e_end; e += 4) {
-    const int32x4 q = __builtin_nontemporal_load(
-        reinterpret_cast<const int32x4*>(indices + e));
-    const int32_t ids[4] = {q[0], q[1], q[2], q[3]};
-#pragma unroll
-    for (int b = 0; b < 4; b += U) {
-      int32_t part[U];
-#pragma unroll
-      for (int i = 0; i < U; ++i) part[i] = ids[b + i];
-      fn(std::integral_constant<int, U>{}, part);
-    }
-  }
-  for (; e < e_end; ++e) {
-    const int32_t one[1] = {indices[e]};
-    fn(std::integral_constant<int, 1>{}, one);
-  }
-}
-
 // ---------------------------------------------------------------------------
 // Forward over the CSR: out[r,h,:] = sum_e w * alpha * zl[u_e,h,:] and
 // lse[r,h], from one gather of zl[u_e] per edge. Online softmax: (m, sum,
@@ -230,14 +204,11 @@ __global__ void __launch_bounds__(256) gatv2_fwd_kernel(
     int64_t H, int64_t D, int64_t nhg, float slope, uint32_t key,
     uint32_t thr, float scale) {
   constexpr int E = NV * VEC;
-  const int64_t wave_global =
-      (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / kWave;
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t nwaves =
-      (static_cast<int64_t>(gridDim.x) * blockDim.x) / kWave;
+  const WaveIds wv = wave_ids();
+  const int lane = wv.lane;
   const int64_t npairs = num_rows * nhg;
 
-  for (int64_t pair = wave_global; pair < npairs; pair += nwaves) {
+  for (int64_t pair = wv.wave_global; pair < npairs; pair += wv.nwaves) {
     int64_t r = pair / nhg;
     if (row_order) r = row_order[r];
     const LaneMap<VEC, NV, SEG> lm(lane, pair % nhg, H, D);
@@ -314,14 +285,11 @@ __global__ void __launch_bounds__(256) gatv2_bwd_dst_kernel(
     float* __restrict__ pa, int64_t num_rows, int64_t F, int64_t H, int64_t D,
     int64_t nhg, float slope, uint32_t key, uint32_t thr, float scale) {
   constexpr int E = NV * VEC;
-  const int64_t wave_global =
-      (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / kWave;
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t nwaves =
-      (static_cast<int64_t>(gridDim.x) * blockDim.x) / kWave;
+  const WaveIds wv = wave_ids();
+  const int lane = wv.lane;
   const int64_t npairs = num_rows * nhg;
 
-  for (int64_t pair = wave_global; pair < npairs; pair += nwaves) {
+  for (int64_t pair = wv.wave_global; pair < npairs; pair += wv.nwaves) {
     int64_t r = pair / nhg;
     if (row_order) r = row_order[r];
     const LaneMap<VEC, NV, SEG> lm(lane, pair % nhg, H, D);
@@ -395,14 +363,11 @@ __global__ void __launch_bounds__(256) gatv2_bwd_src_kernel(
     int64_t num_rows, int64_t F, int64_t H, int64_t D, int64_t nhg,
     float slope, uint32_t key, uint32_t thr, float scale) {
   constexpr int E = NV * VEC;
-  const int64_t wave_global =
-      (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / kWave;
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t nwaves =
-      (static_cast<int64_t>(gridDim.x) * blockDim.x) / kWave;
+  const WaveIds wv = wave_ids();
+  const int lane = wv.lane;
   const int64_t npairs = num_rows * nhg;
 
-  for (int64_t pair = wave_global; pair < npairs; pair += nwaves) {
+  for (int64_t pair = wv.wave_global; pair < npairs; pair += wv.nwaves) {
     int64_t r = pair / nhg;
     if (row_order) r = row_order[r];
     const LaneMap<VEC, NV, SEG> lm(lane, pair % nhg, H, D);
@@ -464,59 +429,15 @@ __global__ void __launch_bounds__(256) gatv2_bwd_src_kernel(
 // host side
 // ---------------------------------------------------------------------------
 
-struct DropArgs {
-  uint32_t key;
-  uint32_t thr;
-  float scale;
-};
+// the shared host checks (attn_util.h), with this op's name in the messages
+constexpr const char* kOp = "gatv2";
 
-DropArgs drop_args(int64_t key, int64_t thr, double scale) {
-  TORCH_CHECK(key >= 0 && key <= 0xFFFFFFFFll && thr >= 0 &&
-                  thr <= 0xFFFFFFFFll,
-              "gatv2: drop_key and drop_thr are 32-bit values");
-  return {static_cast<uint32_t>(key), static_cast<uint32_t>(thr),
-          static_cast<float>(scale)};
-}
-
-const int32_t* row_order_ptr(const torch::Tensor& row_order,
-                             int64_t num_rows) {
-  if (!row_order.defined() || row_order.numel() == 0) return nullptr;
-  TORCH_CHECK(row_order.is_cuda() && row_order.is_contiguous() &&
-                  row_order.numel() == num_rows &&
-                  row_order.scalar_type() == torch::kInt,
-              "gatv2: row_order must be a contiguous int32[num_rows]");
-  return row_order.data_ptr<int32_t>();
-}
-
-void check_graph(const torch::Tensor& indptr, const torch::Tensor& indices) {
-  TORCH_CHECK(indptr.is_cuda() && indices.is_cuda(),
-              "gatv2: graph tensors must be on the device");
-  TORCH_CHECK(indptr.scalar_type() == torch::kLong &&
-                  indices.scalar_type() == torch::kInt,
-              "gatv2: indptr int64 / indices int32");
-  TORCH_CHECK(indptr.is_contiguous() && indices.is_contiguous() &&
-                  indptr.numel() >= 1,
-              "gatv2: graph tensors must be contiguous");
-  // the unrolled edge loop reads indices four at a time with one dwordx4
-  TORCH_CHECK(aligned_to(indices.data_ptr(), 16),
-              "gatv2: indices must be 16-byte aligned");
-}
-
-// a [nodes, F] feature tensor (fp32 or bf16) with at least `rows` rows
+// a [nodes, F] feature tensor whose heads fit the lane layout
 void check_features(const torch::Tensor& x, int64_t rows, int64_t H,
                     const char* name) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous(), "gatv2: ",
-              name, " must be a contiguous [nodes, F] tensor");
-  TORCH_CHECK(x.scalar_type() == torch::kFloat ||
-                  x.scalar_type() == torch::kBFloat16,
-              "gatv2: ", name, " must be fp32 or bf16");
-  TORCH_CHECK(H >= 1 && x.size(1) >= H && x.size(1) % H == 0, "gatv2: ", name,
-              " width F=", x.size(1), " is not H*D for H=", H);
+  attn_util::check_features(kOp, x, rows, H, name);
   TORCH_CHECK(x.size(1) / H <= kMaxHeadDim, "gatv2: head width D=",
               x.size(1) / H, " exceeds the supported ", kMaxHeadDim);
-  TORCH_CHECK(x.size(0) >= rows, "gatv2: ", name, " has ", x.size(0),
-              " rows but the graph references ", rows,
-              " (an under-sized tensor would be an out-of-bounds gather)");
 }
 
 void check_same(const torch::Tensor& x, const torch::Tensor& like,
@@ -532,17 +453,6 @@ void check_attn(const torch::Tensor& attn, int64_t H, int64_t D) {
                   attn.size(0) == H && attn.size(1) == D,
               "gatv2: attn must be a contiguous fp32 [H, D] = [", H, ", ", D,
               "] tensor");
-}
-
-// a per-node per-head fp32 table with at least `rows` rows
-void check_node_table(const torch::Tensor& x, int64_t rows, int64_t H,
-                      const char* name) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous() &&
-                  x.scalar_type() == torch::kFloat && x.size(1) == H,
-              "gatv2: ", name, " must be a contiguous fp32 [nodes, ", H,
-              "] tensor");
-  TORCH_CHECK(x.size(0) >= rows, "gatv2: ", name, " has ", x.size(0),
-              " rows but the graph references ", rows);
 }
 
 // The lane layout of one head width (file header). 4-element accesses need
@@ -606,88 +516,46 @@ T* mptr(torch::Tensor& x) {
   return reinterpret_cast<T*>(x.data_ptr());
 }
 
-template <typename T>
-void fwd_launch(const torch::Tensor& indptr, const torch::Tensor& indices,
-                const torch::Tensor& zl, const torch::Tensor& zr,
-                const torch::Tensor& attn, const int32_t* rop,
-                torch::Tensor& out, torch::Tensor& lse, int64_t H,
-                float slope, DropArgs drop) {
+// fn(T{}) for the element type T of x (fp32 or bf16: check_features)
+template <typename Fn>
+void dispatch_dtype(const torch::Tensor& x, Fn&& fn) {
+  if (x.scalar_type() == torch::kBFloat16)
+    fn(__hip_bfloat16{});
+  else
+    fn(float{});
+}
+
+// One launch of a wave-per-(row, head group) kernel over `indptr`'s rows:
+// the lane layout from the head width and the alignment of `ptrs`, the grid,
+// the launch and its check. kernel_of(VEC, NV, SEG as integral constants)
+// returns the instance; `mid` are the kernel's arguments between the graph
+// and the sizes (the three kernels share what comes before and after).
+template <typename KernelOf, typename... Mid>
+void launch(const torch::Tensor& indptr, const torch::Tensor& indices,
+            const torch::Tensor& zl, int64_t H, const torch::Tensor& attn,
+            std::initializer_list<const void*> ptrs, float slope,
+            DropArgs drop, KernelOf&& kernel_of, Mid... mid) {
   const int64_t num_rows = indptr.numel() - 1, F = zl.size(1), D = F / H;
-  const Layout l = pick_layout(
-      D, sizeof(T), attn, {zl.data_ptr(), zr.data_ptr(), out.data_ptr()});
+  const Layout l = pick_layout(D, zl.element_size(), attn, ptrs);
   dispatch_layout(l, [&](auto vec_c, auto nv_c, auto seg_c) {
-    constexpr int VEC = decltype(vec_c)::value, NV = decltype(nv_c)::value,
-                  SEG = decltype(seg_c)::value;
+    constexpr int SEG = decltype(seg_c)::value;
     const int64_t hpw = kWave / SEG, nhg = (H + hpw - 1) / hpw;
     const int threads = 256;
-    hipLaunchKernelGGL(
-        HIP_KERNEL_NAME(gatv2_fwd_kernel<T, VEC, NV, SEG>),
-        dim3(grid_for(num_rows * nhg, threads)), dim3(threads), 0,
-        current_stream(), indptr.data_ptr<int64_t>(),
-        indices.data_ptr<int32_t>(), cptr<T>(zl), cptr<T>(zr),
-        attn.data_ptr<float>(), rop, mptr<T>(out), lse.data_ptr<float>(),
-        num_rows, F, H, D, nhg, slope, drop.key, drop.thr, drop.scale);
+    hipLaunchKernelGGL(kernel_of(vec_c, nv_c, seg_c),
+                       dim3(grid_for(num_rows * nhg, threads)), dim3(threads),
+                       0, current_stream(), indptr.data_ptr<int64_t>(),
+                       indices.data_ptr<int32_t>(), mid..., num_rows, F, H, D,
+                       nhg, slope, drop.key, drop.thr, drop.scale);
   });
   check_launch();
 }
 
-template <typename T>
-void bwd_dst_launch(const torch::Tensor& indptr, const torch::Tensor& indices,
-                    const torch::Tensor& g, const torch::Tensor& zl,
-                    const torch::Tensor& zr, const torch::Tensor& attn,
-                    const torch::Tensor& lse, const torch::Tensor& t,
-                    const int32_t* rop, torch::Tensor& d_zr,
-                    torch::Tensor& pa, int64_t H, float slope,
-                    DropArgs drop) {
-  const int64_t num_rows = indptr.numel() - 1, F = zl.size(1), D = F / H;
-  const Layout l = pick_layout(
-      D, sizeof(T), attn,
-      {zl.data_ptr(), zr.data_ptr(), g.data_ptr(), d_zr.data_ptr()});
-  dispatch_layout(l, [&](auto vec_c, auto nv_c, auto seg_c) {
-    constexpr int VEC = decltype(vec_c)::value, NV = decltype(nv_c)::value,
-                  SEG = decltype(seg_c)::value;
-    const int64_t hpw = kWave / SEG, nhg = (H + hpw - 1) / hpw;
-    const int threads = 256;
-    hipLaunchKernelGGL(
-        HIP_KERNEL_NAME(gatv2_bwd_dst_kernel<T, VEC, NV, SEG>),
-        dim3(grid_for(num_rows * nhg, threads)), dim3(threads), 0,
-        current_stream(), indptr.data_ptr<int64_t>(),
-        indices.data_ptr<int32_t>(), cptr<T>(g), cptr<T>(zl), cptr<T>(zr),
-        attn.data_ptr<float>(), lse.data_ptr<float>(), t.data_ptr<float>(),
-        rop, mptr<T>(d_zr), pa.data_ptr<float>(), num_rows, F, H, D, nhg,
-        slope, drop.key, drop.thr, drop.scale);
-  });
-  check_launch();
-}
-
-template <typename T>
-void bwd_src_launch(const torch::Tensor& indptr, const torch::Tensor& indices,
-                    const torch::Tensor& g, const torch::Tensor& zl,
-                    const torch::Tensor& zr, const torch::Tensor& attn,
-                    const torch::Tensor& dst_state, const int32_t* rop,
-                    torch::Tensor& d_zl, int64_t H, float slope,
-                    DropArgs drop) {
-  const int64_t num_rows = indptr.numel() - 1, F = zl.size(1), D = F / H;
-  const Layout l = pick_layout(
-      D, sizeof(T), attn,
-      {zl.data_ptr(), zr.data_ptr(), g.data_ptr(), d_zl.data_ptr()});
-  dispatch_layout(l, [&](auto vec_c, auto nv_c, auto seg_c) {
-    constexpr int VEC = decltype(vec_c)::value, NV = decltype(nv_c)::value,
-                  SEG = decltype(seg_c)::value;
-    const int64_t hpw = kWave / SEG, nhg = (H + hpw - 1) / hpw;
-    const int threads = 256;
-    hipLaunchKernelGGL(
-        HIP_KERNEL_NAME(gatv2_bwd_src_kernel<T, VEC, NV, SEG>),
-        dim3(grid_for(num_rows * nhg, threads)), dim3(threads), 0,
-        current_stream(), indptr.data_ptr<int64_t>(),
-        indices.data_ptr<int32_t>(), cptr<T>(g), cptr<T>(zl), cptr<T>(zr),
-        attn.data_ptr<float>(),
-        reinterpret_cast<const f32x2*>(dst_state.data_ptr<float>()), rop,
-        mptr<T>(d_zl), num_rows, F, H, D, nhg, slope, drop.key, drop.thr,
-        drop.scale);
-  });
-  check_launch();
-}
+// kernel_of for launch(): the <T, VEC, NV, SEG> instance of a kernel template
+#define GATV2_KERNEL_OF(kernel, T)                                     \
+  [](auto vec_c, auto nv_c, auto seg_c) {                              \
+    return kernel<T, decltype(vec_c)::value, decltype(nv_c)::value,    \
+                  decltype(seg_c)::value>;                             \
+  }
 
 }  // namespace
 
@@ -696,25 +564,26 @@ std::vector<torch::Tensor> gatv2_fwd_hip(
     torch::Tensor zr, torch::Tensor attn, torch::Tensor row_order,
     int64_t num_cols, int64_t H, double slope, int64_t drop_key,
     int64_t drop_thr, double drop_scale) {
-  check_graph(indptr, indices);
-  const DropArgs drop = drop_args(drop_key, drop_thr, drop_scale);
+  check_graph(kOp, indptr, indices);
+  const DropArgs drop = drop_args(kOp, drop_key, drop_thr, drop_scale);
   const int64_t num_rows = indptr.numel() - 1;
   check_features(zl, num_cols, H, "zl");
   check_features(zr, num_rows, H, "zr");
   check_same(zr, zl, "zr");
   const int64_t F = zl.size(1);
   check_attn(attn, H, F / H);
-  const int32_t* rop = row_order_ptr(row_order, num_rows);
+  const int32_t* rop = row_order_ptr(kOp, row_order, num_rows);
   auto out = torch::empty({num_rows, F}, zl.options());
   auto lse = torch::empty({num_rows, H}, attn.options());
   if (num_rows == 0) return {out, lse};
-  const float sl = static_cast<float>(slope);
-  if (zl.scalar_type() == torch::kBFloat16)
-    fwd_launch<__hip_bfloat16>(indptr, indices, zl, zr, attn, rop, out, lse,
-                               H, sl, drop);
-  else
-    fwd_launch<float>(indptr, indices, zl, zr, attn, rop, out, lse, H, sl,
-                      drop);
+  dispatch_dtype(zl, [&](auto tag) {
+    using T = decltype(tag);
+    launch(indptr, indices, zl, H, attn,
+           {zl.data_ptr(), zr.data_ptr(), out.data_ptr()},
+           static_cast<float>(slope), drop,
+           GATV2_KERNEL_OF(gatv2_fwd_kernel, T), cptr<T>(zl), cptr<T>(zr),
+           attn.data_ptr<float>(), rop, mptr<T>(out), lse.data_ptr<float>());
+  });
   return {out, lse};
 }
 
@@ -723,8 +592,8 @@ std::vector<torch::Tensor> gatv2_bwd_dst_hip(
     torch::Tensor zl, torch::Tensor zr, torch::Tensor attn, torch::Tensor lse,
     torch::Tensor t, torch::Tensor row_order, int64_t num_cols, int64_t H,
     double slope, int64_t drop_key, int64_t drop_thr, double drop_scale) {
-  check_graph(indptr, indices);
-  const DropArgs drop = drop_args(drop_key, drop_thr, drop_scale);
+  check_graph(kOp, indptr, indices);
+  const DropArgs drop = drop_args(kOp, drop_key, drop_thr, drop_scale);
   const int64_t num_rows = indptr.numel() - 1;
   check_features(zl, num_cols, H, "zl");
   check_features(zr, num_rows, H, "zr");
@@ -733,19 +602,21 @@ std::vector<torch::Tensor> gatv2_bwd_dst_hip(
   check_same(g, zl, "g");
   const int64_t F = zl.size(1);
   check_attn(attn, H, F / H);
-  check_node_table(lse, num_rows, H, "lse");
-  check_node_table(t, num_rows, H, "t");
-  const int32_t* rop = row_order_ptr(row_order, num_rows);
+  check_node_table(kOp, lse, num_rows, H, "lse");
+  check_node_table(kOp, t, num_rows, H, "t");
+  const int32_t* rop = row_order_ptr(kOp, row_order, num_rows);
   auto d_zr = torch::empty({num_rows, F}, zl.options());
   auto pa = torch::empty({num_rows, F}, attn.options());
   if (num_rows == 0) return {d_zr, pa};
-  const float sl = static_cast<float>(slope);
-  if (zl.scalar_type() == torch::kBFloat16)
-    bwd_dst_launch<__hip_bfloat16>(indptr, indices, g, zl, zr, attn, lse, t,
-                                   rop, d_zr, pa, H, sl, drop);
-  else
-    bwd_dst_launch<float>(indptr, indices, g, zl, zr, attn, lse, t, rop, d_zr,
-                          pa, H, sl, drop);
+  dispatch_dtype(zl, [&](auto tag) {
+    using T = decltype(tag);
+    launch(indptr, indices, zl, H, attn,
+           {zl.data_ptr(), zr.data_ptr(), g.data_ptr(), d_zr.data_ptr()},
+           static_cast<float>(slope), drop,
+           GATV2_KERNEL_OF(gatv2_bwd_dst_kernel, T), cptr<T>(g), cptr<T>(zl),
+           cptr<T>(zr), attn.data_ptr<float>(), lse.data_ptr<float>(),
+           t.data_ptr<float>(), rop, mptr<T>(d_zr), pa.data_ptr<float>());
+  });
   return {d_zr, pa};
 }
 
@@ -755,8 +626,8 @@ torch::Tensor gatv2_bwd_src_hip(
     torch::Tensor t, torch::Tensor row_order, int64_t num_cols, int64_t H,
     double slope, int64_t drop_key, int64_t drop_thr, double drop_scale) {
   // indptr/indices are the CSC: rows = source nodes, columns = destinations
-  check_graph(indptr, indices);
-  const DropArgs drop = drop_args(drop_key, drop_thr, drop_scale);
+  check_graph(kOp, indptr, indices);
+  const DropArgs drop = drop_args(kOp, drop_key, drop_thr, drop_scale);
   const int64_t num_rows = indptr.numel() - 1;
   check_features(zl, num_rows, H, "zl");
   check_features(zr, num_cols, H, "zr");
@@ -765,9 +636,9 @@ torch::Tensor gatv2_bwd_src_hip(
   check_same(g, zl, "g");
   const int64_t F = zl.size(1);
   check_attn(attn, H, F / H);
-  check_node_table(lse, num_cols, H, "lse");
-  check_node_table(t, num_cols, H, "t");
-  const int32_t* rop = row_order_ptr(row_order, num_rows);
+  check_node_table(kOp, lse, num_cols, H, "lse");
+  check_node_table(kOp, t, num_cols, H, "t");
+  const int32_t* rop = row_order_ptr(kOp, row_order, num_rows);
   auto d_zl = torch::empty({num_rows, F}, zl.options());
   if (num_rows == 0) return d_zl;
   // (lse, t) per destination and head: one 8-byte gather per edge
@@ -776,12 +647,15 @@ torch::Tensor gatv2_bwd_src_hip(
                                 2)
                        .contiguous();
   TORCH_CHECK(aligned_to(dst_state.data_ptr(), 8));
-  const float sl = static_cast<float>(slope);
-  if (zl.scalar_type() == torch::kBFloat16)
-    bwd_src_launch<__hip_bfloat16>(indptr, indices, g, zl, zr, attn,
-                                   dst_state, rop, d_zl, H, sl, drop);
-  else
-    bwd_src_launch<float>(indptr, indices, g, zl, zr, attn, dst_state, rop,
-                          d_zl, H, sl, drop);
+  dispatch_dtype(zl, [&](auto tag) {
+    using T = decltype(tag);
+    launch(indptr, indices, zl, H, attn,
+           {zl.data_ptr(), zr.data_ptr(), g.data_ptr(), d_zl.data_ptr()},
+           static_cast<float>(slope), drop,
+           GATV2_KERNEL_OF(gatv2_bwd_src_kernel, T), cptr<T>(g), cptr<T>(zl),
+           cptr<T>(zr), attn.data_ptr<float>(),
+           reinterpret_cast<const f32x2*>(dst_state.data_ptr<float>()), rop,
+           mptr<T>(d_zl));
+  });
   return d_zl;
 }

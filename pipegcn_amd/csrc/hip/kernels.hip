@@ -28,15 +28,8 @@
 
 namespace {
 
-constexpr int kWave = 64;
-
-using int32x4 = __attribute__((ext_vector_type(4))) int;
-
-// element-type helpers: compute in fp32, store in T (fp32 or bf16)
-__device__ __forceinline__ float to_f32(float v) { return v; }
-__device__ __forceinline__ float to_f32(__hip_bfloat16 v) {
-  return __bfloat162float(v);
-}
+// element-type helpers: compute in fp32 (to_f32, hip_util.h), store in T
+// (fp32 or bf16)
 __device__ __forceinline__ void st_nt(float* p, float v) {
   __builtin_nontemporal_store(v, p);
 }
@@ -181,11 +174,7 @@ void launch_spmm(const int64_t* indptr, const int32_t* indices,
   const int64_t nchunks = (F + kWave * VEC - 1) / (kWave * VEC);
   constexpr int threads = 256;  // 4 whole waves: the kernel keeps the
   static_assert(threads % kWave == 0);  // wave index in a scalar register
-  const int64_t npairs = num_rows * nchunks;
-  int64_t blocks = (npairs * kWave + threads - 1) / threads;
-  // cap the grid; the grid-stride loop covers the rest
-  blocks = std::min<int64_t>(blocks, 8 * 65536);
-  if (blocks == 0) blocks = 1;
+  const int64_t blocks = grid_for(num_rows * nchunks, threads);
   auto launch = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), 0, stream, indptr,
                        indices, feat, dst_scale, src_scale, row_order, out,
@@ -244,9 +233,7 @@ void launch_rowcopy(const T* src, const int64_t* idx, T* dst,
                     int64_t nrows, int64_t F, hipStream_t stream) {
   const int64_t nchunks = (F + kWave * VEC - 1) / (kWave * VEC);
   const int threads = 256;
-  int64_t blocks = (nrows * nchunks * kWave + threads - 1) / threads;
-  blocks = std::min<int64_t>(blocks, 8 * 65536);
-  if (blocks == 0) blocks = 1;
+  const int64_t blocks = grid_for(nrows * nchunks, threads);
   hipLaunchKernelGGL(HIP_KERNEL_NAME(rowcopy_kernel<T, VEC, SCATTER_ADD>),
                      dim3(blocks), dim3(threads), 0, stream, src, idx, dst,
                      nrows, F, nchunks);

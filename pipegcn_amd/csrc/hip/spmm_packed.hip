@@ -33,10 +33,6 @@
 
 namespace {
 
-constexpr int kWave = 64;
-
-using int32x4 = __attribute__((ext_vector_type(4))) int;
-
 // ---------------------------------------------------------------------------
 // Pack: one wave per row, 64 columns (two header entries) per step.
 // ---------------------------------------------------------------------------
@@ -373,10 +369,8 @@ void pack_rows_hip(torch::Tensor x, torch::Tensor packed) {
                   packed.size(1) == l.stride_words,
               "pack_rows: packed must be int32 [N, stride_words]");
   const int threads = 256;  // 4 waves, one row each
-  int64_t blocks = (N * kWave + threads - 1) / threads;
-  blocks = std::min<int64_t>(blocks, 8 * 65536);
-  if (blocks == 0) blocks = 1;
-  hipLaunchKernelGGL(pack_rows_kernel, dim3(blocks), dim3(threads), 0,
+  hipLaunchKernelGGL(pack_rows_kernel, dim3(grid_for(N, threads)),
+                     dim3(threads), 0,
                      current_stream(), x.data_ptr<float>(),
                      reinterpret_cast<uint32_t*>(packed.data_ptr<int32_t>()),
                      N, F, l.stride_words, l.hdr_words);
@@ -431,14 +425,10 @@ void spmm_packed_hip(torch::Tensor indptr, torch::Tensor indices,
       const int64_t nchunks = (F + kWave * VEC - 1) / (kWave * VEC);
       constexpr int threads = 256;  // 4 whole waves: the kernel keeps the
       static_assert(threads % kWave == 0);  // wave index in a scalar register
-      const int64_t npairs = num_rows * nchunks;
-      int64_t blocks = (npairs * kWave + threads - 1) / threads;
-      blocks = std::min<int64_t>(blocks, 8 * 65536);
-      if (blocks == 0) blocks = 1;
       hipLaunchKernelGGL(HIP_KERNEL_NAME(spmm_packed_kernel<VEC>),
-                         dim3(blocks), dim3(threads), 0, stream, ip, xp, pp,
-                         l.stride_words, l.hdr_words, dsp, rop, op, num_rows,
-                         F, nchunks);
+                         dim3(grid_for(num_rows * nchunks, threads)),
+                         dim3(threads), 0, stream, ip, xp, pp, l.stride_words,
+                         l.hdr_words, dsp, rop, op, num_rows, F, nchunks);
     }
   });
   check_launch();

@@ -36,7 +36,6 @@ from pipegcn_amd import ops
 from pipegcn_amd.graph.csr import FullGraph, HaloGraph
 from pipegcn_amd.models.gat import NEGATIVE_SLOPE
 from pipegcn_amd.models.sage import GNNBase
-from pipegcn_amd.parallel import context as ctx
 
 
 class GATv2Layer(nn.Module):
@@ -102,39 +101,10 @@ class GATv2(GNNBase):
         if use_pp:
             raise NotImplementedError("--use-pp supports graphsage only "
                                       "(reference parity)")
-        super().__init__(layer_size, activation, False, dropout, norm,
-                         n_linear)
-        from pipegcn_amd.models.sync_bn import SyncBatchNorm
+        super().__init__(layer_size, activation, dropout, norm, train_size,
+                         n_linear, n_heads=n_heads, attn_drop=attn_drop)
 
-        for i in range(self.n_layers):
-            if i < self.n_layers - self.n_linear:
-                heads = 1 if i == self.n_layers - 1 else n_heads
-                self.layers.append(GATv2Layer(layer_size[i],
-                                              layer_size[i + 1],
-                                              num_heads=heads,
-                                              attn_drop=attn_drop))
-            else:
-                self.layers.append(nn.Linear(layer_size[i],
-                                             layer_size[i + 1]))
-            if i < self.n_layers - 1 and self.use_norm:
-                if norm == "layer":
-                    self.norm.append(nn.LayerNorm(layer_size[i + 1],
-                                                  elementwise_affine=True))
-                elif norm == "batch":
-                    self.norm.append(SyncBatchNorm(layer_size[i + 1],
-                                                   train_size))
-
-    def forward(self, g, feat, in_deg=None):
-        h = feat
-        for i in range(self.n_layers):
-            if i < self.n_layers - self.n_linear:
-                if self.training:
-                    h = ctx.buffer.update(i, h)
-                h = self._drop(h)
-                h = self.layers[i](g, h)
-            else:
-                h = self._drop(h)
-                h = ops.linear(h, self.layers[i])
-            if i < self.n_layers - 1:
-                h = self._norm_act(i, h)
-        return h
+    def make_conv(self, i, in_feats, out_feats, n_heads, attn_drop):
+        heads = 1 if i == self.n_layers - 1 else n_heads
+        return GATv2Layer(in_feats, out_feats, num_heads=heads,
+                          attn_drop=attn_drop)

@@ -19,7 +19,6 @@ from torch import nn
 from pipegcn_amd import ops
 from pipegcn_amd.graph.csr import FullGraph, HaloGraph
 from pipegcn_amd.models.sage import GNNBase
-from pipegcn_amd.parallel import context as ctx
 
 
 class _SpmmSym(torch.autograd.Function):
@@ -92,36 +91,8 @@ class GCN(GNNBase):
         if use_pp:
             raise NotImplementedError("--use-pp supports graphsage only "
                                       "(reference parity)")
-        super().__init__(layer_size, activation, False, dropout, norm,
+        super().__init__(layer_size, activation, dropout, norm, train_size,
                          n_linear)
-        from pipegcn_amd.models.sync_bn import SyncBatchNorm
 
-        for i in range(self.n_layers):
-            if i < self.n_layers - self.n_linear:
-                self.layers.append(GCNLayer(layer_size[i],
-                                            layer_size[i + 1]))
-            else:
-                self.layers.append(nn.Linear(layer_size[i],
-                                             layer_size[i + 1]))
-            if i < self.n_layers - 1 and self.use_norm:
-                if norm == "layer":
-                    self.norm.append(nn.LayerNorm(layer_size[i + 1],
-                                                  elementwise_affine=True))
-                elif norm == "batch":
-                    self.norm.append(SyncBatchNorm(layer_size[i + 1],
-                                                   train_size))
-
-    def forward(self, g, feat, in_deg=None):
-        h = feat
-        for i in range(self.n_layers):
-            if i < self.n_layers - self.n_linear:
-                if self.training:
-                    h = ctx.buffer.update(i, h)
-                h = self._drop(h)
-                h = self.layers[i](g, h, in_deg)
-            else:
-                h = self._drop(h)
-                h = ops.linear(h, self.layers[i])
-            if i < self.n_layers - 1:
-                h = self._norm_act(i, h)
-        return h
+    def make_conv(self, i, in_feats, out_feats):
+        return GCNLayer(in_feats, out_feats)

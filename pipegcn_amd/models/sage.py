@@ -71,18 +71,65 @@ class GraphSAGELayer(nn.Module):
 
 
 class GNNBase(nn.Module):
-    def __init__(self, layer_size, activation, use_pp=False, dropout=0.5,
-                 norm="layer", n_linear=0):
+    """Conv layers, then `n_linear` linear layers, with norm + activation
+    between layers; `ctx.buffer.update` is the only distributed seam.
+
+    A model subclasses this with `make_conv(i, in_feats, out_feats, **conv)`,
+    which builds conv layer i from the keyword arguments the subclass handed
+    to this constructor. Layer i is built before norm i, so the parameter
+    draws and the state_dict keys (`layers.N.*`, `norm.N.*`) follow the layer
+    index.
+    """
+
+    def __init__(self, layer_size, activation, dropout=0.5, norm="layer",
+                 train_size=None, n_linear=0, **conv):
         super().__init__()
         self.n_layers = len(layer_size) - 1
         self.layers = nn.ModuleList()
         self.activation = activation
-        self.use_pp = use_pp
         self.n_linear = n_linear
         self.use_norm = norm is not None
         if self.use_norm:
             self.norm = nn.ModuleList()
         self.dropout = nn.Dropout(p=dropout)
+        for i in range(self.n_layers):
+            if i < self.n_layers - n_linear:
+                self.layers.append(self.make_conv(i, layer_size[i],
+                                                  layer_size[i + 1], **conv))
+            else:
+                self.layers.append(nn.Linear(layer_size[i],
+                                             layer_size[i + 1]))
+            if i < self.n_layers - 1 and self.use_norm:
+                if norm == "layer":
+                    self.norm.append(
+                        nn.LayerNorm(layer_size[i + 1],
+                                     elementwise_affine=True))
+                elif norm == "batch":
+                    self.norm.append(SyncBatchNorm(layer_size[i + 1],
+                                                   train_size))
+
+    def make_conv(self, i, in_feats, out_feats, **conv):
+        raise NotImplementedError
+
+    def _exchanges_input(self, i):
+        """Whether conv layer i's training input goes through the halo
+        exchange of `ctx.buffer.update`."""
+        return True
+
+    def forward(self, g, feat, in_deg=None):
+        h = feat
+        for i in range(self.n_layers):
+            if i < self.n_layers - self.n_linear:
+                if self.training and self._exchanges_input(i):
+                    h = ctx.buffer.update(i, h)
+                h = self._drop(h)
+                h = self.layers[i](g, h, in_deg)
+            else:
+                h = self._drop(h)
+                h = ops.linear(h, self.layers[i])
+            if i < self.n_layers - 1:
+                h = self._norm_act(i, h)
+        return h
 
     def _drop(self, h):
         """Dropout: fused bitmask kernel on GPU, eager elsewhere."""
@@ -105,37 +152,15 @@ class GNNBase(nn.Module):
 class GraphSAGE(GNNBase):
     def __init__(self, layer_size, activation, use_pp, dropout=0.5,
                  norm="layer", train_size=None, n_linear=0):
-        super().__init__(layer_size, activation, use_pp, dropout, norm,
-                         n_linear)
-        for i in range(self.n_layers):
-            if i < self.n_layers - self.n_linear:
-                self.layers.append(
-                    GraphSAGELayer(layer_size[i], layer_size[i + 1],
-                                   use_pp=use_pp))
-            else:
-                self.layers.append(nn.Linear(layer_size[i],
-                                             layer_size[i + 1]))
-            if i < self.n_layers - 1 and self.use_norm:
-                if norm == "layer":
-                    self.norm.append(
-                        nn.LayerNorm(layer_size[i + 1],
-                                     elementwise_affine=True))
-                elif norm == "batch":
-                    self.norm.append(SyncBatchNorm(layer_size[i + 1],
-                                                   train_size))
-            use_pp = False
+        super().__init__(layer_size, activation, dropout, norm, train_size,
+                         n_linear, use_pp=use_pp)
+        self.use_pp = use_pp
 
-    def forward(self, g, feat, in_deg=None):
-        h = feat
-        for i in range(self.n_layers):
-            if i < self.n_layers - self.n_linear:
-                if self.training and (i > 0 or not self.use_pp):
-                    h = ctx.buffer.update(i, h)
-                h = self._drop(h)
-                h = self.layers[i](g, h, in_deg)
-            else:
-                h = self._drop(h)
-                h = ops.linear(h, self.layers[i])
-            if i < self.n_layers - 1:
-                h = self._norm_act(i, h)
-        return h
+    def make_conv(self, i, in_feats, out_feats, use_pp):
+        # use_pp applies to the first layer only: its input already holds
+        # [feat ‖ mean_agg], precomputed once
+        return GraphSAGELayer(in_feats, out_feats, use_pp=use_pp and i == 0)
+
+    def _exchanges_input(self, i):
+        # a use_pp first layer aggregates nothing, so it fetches no halo rows
+        return i > 0 or not self.use_pp

@@ -20,6 +20,12 @@ from pipegcn_amd import native
 from pipegcn_amd.graph.csr import CSR, HaloGraph
 
 
+def _row_order(matrix: CSR) -> torch.Tensor:
+    """The matrix's row order as the kernels take it: an empty tensor stands
+    for natural order."""
+    return matrix.row_order if matrix.row_order is not None else torch.Tensor()
+
+
 def _tune_row_order(csr: CSR, feat, s, ss) -> bool:
     """One-shot A/B of LPT vs natural row order for this (graph, F).
 
@@ -60,7 +66,7 @@ def spmm(csr: CSR, feat: torch.Tensor,
     s = scale if scale is not None else torch.Tensor()
     ss = src_scale if src_scale is not None else torch.Tensor()
     feat = feat.contiguous()
-    ro = csr.row_order if csr.row_order is not None else torch.Tensor()
+    ro = _row_order(csr)
     # auto-tuned row order on real-sized GPU workloads (>= ~1G gathered
     # elements, where a kernel is multi-ms and the 6 extra timed launches
     # vanish into warmup); PIPEGCN_SPMM_AUTOTUNE=0 pins LPT
@@ -203,7 +209,7 @@ def spmm_packed(csr: CSR, feat: torch.Tensor,
     s = scale if scale is not None else torch.Tensor()
     # the dense path's row order: its cached autotune decision for this
     # (graph, F) if it made one, else the LPT order (no second autotune)
-    ro = csr.row_order if csr.row_order is not None else torch.Tensor()
+    ro = _row_order(csr)
     if getattr(csr, "_lpt_choice", {}).get(feat.shape[1]) is False:
         ro = torch.Tensor()
     packed = native().pack_rows(feat.contiguous())
@@ -329,33 +335,61 @@ def gat_dropout_keep(u: torch.Tensor, v: torch.Tensor, num_heads: int,
     return _gat_keep_hash(u, v, num_heads, key) >= thr
 
 
+def _attn_dropout(op: str, attn_drop: float, seed: Optional[int]):
+    """(key, thr, scale) of one `op` call; (0, 0, 1.0) is no dropout. Checks
+    attn_drop and, when it is positive and no seed is given, draws one from
+    torch's host generator (as fused_dropout: no device sync)."""
+    if not 0.0 <= attn_drop < 1.0:
+        raise ValueError(f"{op}: attn_drop={attn_drop} is outside [0, 1)")
+    if attn_drop == 0.0:
+        return 0, 0, 1.0
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    return _gat_dropout_params(seed, attn_drop)
+
+
+def _edge_endpoints(csr: CSR):
+    """(u, v) int64 [nnz]: source and destination of every edge, CSR order."""
+    deg = csr.indptr[1:] - csr.indptr[:-1]
+    v = torch.repeat_interleave(
+        torch.arange(csr.num_rows, device=csr.indices.device), deg)
+    return csr.indices.long(), v
+
+
+def _edge_softmax_aggregate_torch(csr: CSR, u, v, score, values, drop=None):
+    """The common tail of the two CPU references: softmax of score [nnz, H]
+    over the edges of each destination, optional attention dropout, then
+    out[v] += alpha * values [nnz, H, D]. Returns fp32 [rows, H * D]."""
+    rows, num_heads = csr.num_rows, score.shape[1]
+    # the row maximum is a shift only (softmax is invariant to it)
+    m = torch.zeros(rows, num_heads, device=score.device).scatter_reduce(
+        0, v.unsqueeze(1).expand_as(score), score.detach(), "amax",
+        include_self=False)
+    ex = torch.exp(score - m.index_select(0, v))
+    den = torch.zeros(rows, num_heads, device=score.device).index_add(0, v, ex)
+    alpha = ex / den.index_select(0, v)
+    if drop is not None:
+        key, thr, scale = drop
+        keep = _gat_keep_hash(u, v, num_heads, key) >= thr
+        alpha = alpha * (keep.to(alpha.dtype) * scale)
+    out = torch.zeros(rows, num_heads, values.shape[2], device=score.device)
+    out = out.index_add(0, v, alpha.unsqueeze(-1) * values)
+    return out.view(rows, -1)
+
+
 def _gat_aggregate_torch(csr: CSR, z, el, er, num_heads: int, slope: float,
                          drop=None):
     """Edge-softmax aggregation composed from torch ops under ordinary
     autograd: the CPU test tier and rank-0 eval. [nnz, H] temporaries are
     fine here; the GPU path never makes them. drop = (key, thr, scale)
     applies the attention-dropout mask the kernels would draw."""
-    rows = csr.num_rows
-    deg = csr.indptr[1:] - csr.indptr[:-1]
-    v = torch.repeat_interleave(torch.arange(rows, device=z.device), deg)
-    u = csr.indices.long()
+    u, v = _edge_endpoints(csr)
     zf = z.float().view(z.shape[0], num_heads, -1)
     e = torch.nn.functional.leaky_relu(
         el.float().index_select(0, u) + er.float().index_select(0, v), slope)
-    # the row maximum is a shift only (softmax is invariant to it)
-    m = torch.zeros(rows, num_heads, device=z.device).scatter_reduce(
-        0, v.unsqueeze(1).expand_as(e), e.detach(), "amax",
-        include_self=False)
-    ex = torch.exp(e - m.index_select(0, v))
-    den = torch.zeros(rows, num_heads, device=z.device).index_add(0, v, ex)
-    alpha = ex / den.index_select(0, v)
-    if drop is not None:
-        key, thr, scale = drop
-        keep = _gat_keep_hash(u, v, num_heads, key) >= thr
-        alpha = alpha * (keep.to(alpha.dtype) * scale)
-    out = torch.zeros(rows, num_heads, zf.shape[2], device=z.device)
-    out = out.index_add(0, v, alpha.unsqueeze(-1) * zf.index_select(0, u))
-    return out.view(rows, -1).to(z.dtype)
+    out = _edge_softmax_aggregate_torch(csr, u, v, e, zf.index_select(0, u),
+                                        drop)
+    return out.to(z.dtype)
 
 
 def _gat_forward_hip(csr: CSR, z, el, er, num_heads, slope, with_aux,
@@ -363,7 +397,7 @@ def _gat_forward_hip(csr: CSR, z, el, er, num_heads, slope, with_aux,
     """row stats + aggregation on the gfx950 kernels -> (lse, out[, zc,
     csum]). Uses csr.row_order as given (no lazy autotune here). drop =
     (key, thr, scale); thr 0 is no attention dropout."""
-    ro = csr.row_order if csr.row_order is not None else torch.Tensor()
+    ro = _row_order(csr)
     lse = native().gat_row_stats(csr.indptr, csr.indices, el, er,
                                  csr.num_cols, slope)
     res = native().gat_aggregate_fwd(csr.indptr, csr.indices, z, el, er, lse,
@@ -404,7 +438,7 @@ class _GatAggregate(torch.autograd.Function):
         # [num_in, F], no gather — plain torch ops
         t = (gh * out.view(n, H, -1).float()).sum(-1)
         d_er = (gh * zc.view(n, H, -1).float()).sum(-1) - t * csum
-        ro = csc.row_order if csc.row_order is not None else torch.Tensor()
+        ro = _row_order(csc)
         dz, d_el = native().gat_aggregate_bwd(
             csc.indptr, csc.indices, g, z, el, er, lse, t, ro, csc.num_cols,
             H, ctx.slope, *ctx.drop)
@@ -436,16 +470,8 @@ def gat_aggregate(graph: HaloGraph, z: torch.Tensor, el: torch.Tensor,
     seed < 2^62) defaults to a draw from torch's host generator, so runs are
     reproducible under torch.manual_seed; attn_drop == 0 draws nothing.
     """
-    if not 0.0 <= attn_drop < 1.0:
-        raise ValueError(
-            f"gat_aggregate: attn_drop={attn_drop} is outside [0, 1)")
+    drop = _attn_dropout("gat_aggregate", attn_drop, seed)
     _gat_check(graph.csr, z, el, er, num_heads)
-    drop = (0, 0, 1.0)
-    if attn_drop > 0.0:
-        if seed is None:
-            # host-drawn, as fused_dropout: no device sync
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        drop = _gat_dropout_params(seed, attn_drop)
     if not z.is_cuda:
         return _gat_aggregate_torch(graph.csr, z, el, er, num_heads, slope,
                                     drop if drop[1] > 0 else None)
@@ -511,27 +537,11 @@ def _gatv2_aggregate_torch(csr: CSR, zl, zr, attn, num_heads: int,
     autograd: the CPU test tier and rank-0 eval. [nnz, H, D] temporaries are
     fine here; the GPU path never makes them. drop = (key, thr, scale)
     applies the attention-dropout mask the kernels would draw."""
-    rows = csr.num_rows
-    deg = csr.indptr[1:] - csr.indptr[:-1]
-    v = torch.repeat_interleave(torch.arange(rows, device=zl.device), deg)
-    u = csr.indices.long()
+    u, v = _edge_endpoints(csr)
     zlu = zl.float().view(zl.shape[0], num_heads, -1).index_select(0, u)
-    x = zlu + zr.float().view(rows, num_heads, -1).index_select(0, v)
+    x = zlu + zr.float().view(csr.num_rows, num_heads, -1).index_select(0, v)
     s = (torch.nn.functional.leaky_relu(x, slope) * attn.float()).sum(-1)
-    # the row maximum is a shift only (softmax is invariant to it)
-    m = torch.zeros(rows, num_heads, device=zl.device).scatter_reduce(
-        0, v.unsqueeze(1).expand_as(s), s.detach(), "amax",
-        include_self=False)
-    ex = torch.exp(s - m.index_select(0, v))
-    den = torch.zeros(rows, num_heads, device=zl.device).index_add(0, v, ex)
-    alpha = ex / den.index_select(0, v)
-    if drop is not None:
-        key, thr, scale = drop
-        keep = _gat_keep_hash(u, v, num_heads, key) >= thr
-        alpha = alpha * (keep.to(alpha.dtype) * scale)
-    out = torch.zeros(rows, num_heads, zlu.shape[2], device=zl.device)
-    out = out.index_add(0, v, alpha.unsqueeze(-1) * zlu)
-    return out.view(rows, -1).to(zl.dtype)
+    return _edge_softmax_aggregate_torch(csr, u, v, s, zlu, drop).to(zl.dtype)
 
 
 def _gatv2_forward_hip(csr: CSR, zl, zr, attn, num_heads, slope,
@@ -539,7 +549,7 @@ def _gatv2_forward_hip(csr: CSR, zl, zr, attn, num_heads, slope,
     """One gather pass on the gfx950 kernel -> (out, lse). Uses
     csr.row_order as given. drop = (key, thr, scale); thr 0 is no attention
     dropout."""
-    ro = csr.row_order if csr.row_order is not None else torch.Tensor()
+    ro = _row_order(csr)
     return native().gatv2_fwd(csr.indptr, csr.indices, zl, zr, attn, ro,
                               csr.num_cols, num_heads, slope, *drop)
 
@@ -573,14 +583,11 @@ class _Gatv2Aggregate(torch.autograd.Function):
         # per-node per-head dot: an elementwise pass over [num_in, F]
         t = (g.view(n, H, -1).float() * out.view(n, H, -1).float()).sum(-1)
 
-        def order(m):
-            return m.row_order if m.row_order is not None else torch.Tensor()
-
         d_zr, pa = native().gatv2_bwd_dst(
-            csr.indptr, csr.indices, g, zl, zr, attn, lse, t, order(csr),
+            csr.indptr, csr.indices, g, zl, zr, attn, lse, t, _row_order(csr),
             csr.num_cols, H, ctx.slope, *ctx.drop)
         d_zl = native().gatv2_bwd_src(
-            csc.indptr, csc.indices, g, zl, zr, attn, lse, t, order(csc),
+            csc.indptr, csc.indices, g, zl, zr, attn, lse, t, _row_order(csc),
             csc.num_cols, H, ctx.slope, *ctx.drop)
         d_attn = native().colsum(pa).view_as(attn)
         if d_zl.shape[0] < zl.shape[0]:  # rows the graph never references
@@ -609,16 +616,8 @@ def gatv2_aggregate(graph: HaloGraph, zl: torch.Tensor, zr: torch.Tensor,
     (`gat_dropout_keep`), applied after the softmax, recomputed in every
     pass; attn_drop == 0 draws nothing from the generator.
     """
-    if not 0.0 <= attn_drop < 1.0:
-        raise ValueError(
-            f"gatv2_aggregate: attn_drop={attn_drop} is outside [0, 1)")
+    drop = _attn_dropout("gatv2_aggregate", attn_drop, seed)
     _gatv2_check(graph.csr, zl, zr, attn, num_heads)
-    drop = (0, 0, 1.0)
-    if attn_drop > 0.0:
-        if seed is None:
-            # host-drawn, as fused_dropout: no device sync
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        drop = _gat_dropout_params(seed, attn_drop)
     if not zl.is_cuda:
         return _gatv2_aggregate_torch(graph.csr, zl, zr, attn, num_heads,
                                       slope, drop if drop[1] > 0 else None)
