@@ -8,16 +8,21 @@
 
 #include "common.h"
 
+#include <optional>
+
 static torch::Tensor spmm(torch::Tensor indptr, torch::Tensor indices,
                           torch::Tensor feat, torch::Tensor dst_scale,
                           torch::Tensor src_scale, torch::Tensor row_order,
-                          int64_t num_rows) {
+                          int64_t num_rows,
+                          std::optional<torch::Tensor> n_live) {
   if (feat.is_cuda()) {
     auto out = torch::empty({num_rows, feat.size(1)}, feat.options());
     spmm_csr_hip(indptr, indices, feat, dst_scale, src_scale, row_order,
-                 out);
+                 out, n_live.value_or(torch::Tensor()));
     return out;
   }
+  // n_live only saves the GPU kernel memory traffic: the CPU result is the
+  // same with or without it
   if (feat.scalar_type() == torch::kBFloat16) {
     // CPU tier computes in fp32 (the CPU path serves tests + rank-0 eval)
     return spmm_cpu(indptr, indices, feat.to(torch::kFloat), dst_scale,
@@ -25,6 +30,18 @@ static torch::Tensor spmm(torch::Tensor indptr, torch::Tensor indices,
         .to(torch::kBFloat16);
   }
   return spmm_cpu(indptr, indices, feat, dst_scale, src_scale, num_rows);
+}
+
+// GPU-only (ops._SpmmMean.backward multiplies eagerly on the CPU)
+static std::vector<torch::Tensor> scale_rows_live(torch::Tensor g,
+                                                  torch::Tensor inv) {
+  TORCH_CHECK(g.is_cuda() && g.dim() == 2,
+              "scale_rows_live is the GPU path");
+  if (g.size(0) > 1 && g.size(1) > 1 && g.stride(1) != 1) g = g.contiguous();
+  auto scaled = torch::empty({g.size(0), g.size(1)}, g.options());
+  auto n_live = torch::empty({1}, g.options().dtype(torch::kInt));
+  scale_rows_live_hip(g, inv, scaled, n_live);
+  return {scaled, n_live};
 }
 
 // GPU-only: ops.pack_rows_reference is the torch mirror of the layout
@@ -156,7 +173,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("build_csr", &build_csr, "COO -> CSR (counting sort by dst)");
   m.def("partition_graph", &partition_graph_cpu,
         "BFS-grown + refined k-way partitioner (cut/vol objective)");
-  m.def("spmm", &spmm, "CSR SpMM with fused scale epilogue (fwd & transpose)");
+  // n_live trails with a default: calls without it run what they ran before
+  m.def("spmm", &spmm, "CSR SpMM with fused scale epilogue (fwd & transpose)",
+        py::arg("indptr"), py::arg("indices"), py::arg("feat"),
+        py::arg("dst_scale"), py::arg("src_scale"), py::arg("row_order"),
+        py::arg("num_rows"), py::arg("n_live") = py::none());
+  m.def("scale_rows_live", &scale_rows_live,
+        "g * inv per row -> (scaled, n_live = 1 + last non-zero row, int32)");
   m.def("pack_rows", &pack_rows,
         "fp32 [N, F] -> packed rows int32 [N, stride_words]");
   m.def("spmm_packed", &spmm_packed,

@@ -47,10 +47,22 @@ torch::Tensor spmm_cpu(torch::Tensor indptr, torch::Tensor indices,
 
 // out[r,:] = scale[r] * sum_{e in [indptr[r], indptr[r+1])} feat[indices[e],:]
 // All tensors on device. feat fp32 [num_src, F], out fp32 [num_rows, F].
+// n_live (optional: undefined or empty is none; not with src_scale): one int32
+// in device memory, read by the kernel. The caller guarantees that the rows of
+// feat from *n_live on are all zero; their gathers are then redirected to row
+// *n_live. The result is bitwise the one without it.
 void spmm_csr_hip(torch::Tensor indptr, torch::Tensor indices,
                   torch::Tensor feat, torch::Tensor dst_scale,
                   torch::Tensor src_scale, torch::Tensor row_order,
-                  torch::Tensor out);
+                  torch::Tensor out, torch::Tensor n_live = {});
+
+// scaled[r,:] = g[r,:] * inv[r] (for bf16, inv rounded to bf16 first, as the
+// eager product rounds it), and in the same pass *n_live = 1 + the largest r
+// with any scaled[r,c] != 0, or 0 (both zeros are zero, NaN and Inf are not).
+// g fp32 or bf16 [N, F] with unit column stride (rows may be strided), inv
+// fp32 [N]; scaled is contiguous, n_live one int32, zeroed here.
+void scale_rows_live_hip(torch::Tensor g, torch::Tensor inv,
+                         torch::Tensor scaled, torch::Tensor n_live);
 
 // Packed rows (csrc/hip/spmm_packed.hip): one fixed-stride record per row of a
 // fp32 [N, F] tensor, in 4-byte words: mask_words header entries {uint32 mask,

@@ -3,6 +3,8 @@
 //   1. dropout fwd/bwd with a BITPACKED mask (1 bit/element instead of
 //      torch's 1 byte/element — 8x less mask memory, one fused pass)
 //   2. LayerNorm [+ fused ReLU] fwd/bwd, wave-per-row
+//   3. the backward SpMM's row pre-scale, which also finds where the
+//      gradient's all-zero tail starts (scale_rows_live_kernel)
 //
 // Replaces the eager torch dropout / nn.LayerNorm / F.relu between layers
 // (reference sites: /root/reference/module/model.py:47,53-56). Fusing
@@ -327,7 +329,182 @@ __global__ void ln_bwd_kernel(const T* __restrict__ dy,
   }
 }
 
+// ---------------------------------------------------------------------------
+// Row scale + live-row count (the pre-scale of the backward SpMM): one pass
+// writes scaled[r,:] = g[r,:] * inv[r] and finds n_live = 1 + the last row
+// of scaled with a non-zero in it. One wave per (row, 64 * VEC column chunk),
+// grid-stride, four pairs' loads in flight per wave. A lane keeps the last
+// live row it saw, the block reduces in LDS and issues ONE integer atomicMax
+// — order-independent, so the count is reproducible.
+// Elements are handled as raw bits so that the product is bit for bit the
+// eager one: fp32 is one multiply; bf16 multiplies in fp32 by inv rounded to
+// bf16 and rounds to nearest even, NaN to 0x7FC0, as torch's bf16 does.
+// ---------------------------------------------------------------------------
+
+template <typename T>
+struct RowScaleElem;
+template <>
+struct RowScaleElem<float> {
+  using raw = float;
+  static __device__ __forceinline__ float scale(float inv) { return inv; }
+  static __device__ __forceinline__ float mul(float v, float s) {
+    return v * s;
+  }
+  static __device__ __forceinline__ bool nonzero(float v) { return v != 0.f; }
+};
+template <>
+struct RowScaleElem<__hip_bfloat16> {
+  using raw = unsigned short;
+  static __device__ __forceinline__ unsigned short round(float f) {
+    const uint32_t b = __float_as_uint(f);
+    if (f != f) return 0x7FC0;
+    return static_cast<unsigned short>((b + 0x7FFFu + ((b >> 16) & 1u)) >> 16);
+  }
+  static __device__ __forceinline__ float widen(unsigned short h) {
+    return __uint_as_float(static_cast<uint32_t>(h) << 16);
+  }
+  static __device__ __forceinline__ float scale(float inv) {
+    return widen(round(inv));
+  }
+  static __device__ __forceinline__ unsigned short mul(unsigned short v,
+                                                       float s) {
+    return round(widen(v) * s);
+  }
+  static __device__ __forceinline__ bool nonzero(unsigned short v) {
+    return (v & 0x7FFFu) != 0;
+  }
+};
+
+// VEC elements moved with one load/store; the caller picks VEC so that
+// every row start and F are multiples of it
+template <typename R, int VEC>
+struct alignas(sizeof(R) * VEC) RowScalePack {
+  R v[VEC];
+};
+
+constexpr int kScaleInFlight = 4;
+
+template <typename T, int VEC>
+__global__ void scale_rows_live_kernel(const T* __restrict__ g,
+                                       const float* __restrict__ inv,
+                                       T* __restrict__ scaled,
+                                       int32_t* __restrict__ n_live,
+                                       int64_t N, int64_t F,
+                                       int64_t g_stride, int64_t nchunks) {
+  using E = RowScaleElem<T>;
+  using Pack = RowScalePack<typename E::raw, VEC>;
+  __shared__ int blk_live;
+  if (threadIdx.x == 0) blk_live = 0;
+  __syncthreads();
+
+  const int wave_in_block =
+      __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave);
+  const int64_t waves_per_block = blockDim.x / kWave;
+  const int64_t wave_global =
+      static_cast<int64_t>(blockIdx.x) * waves_per_block + wave_in_block;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t nwaves = static_cast<int64_t>(gridDim.x) * waves_per_block;
+  const int64_t npairs = N * nchunks;
+  const auto* gp = reinterpret_cast<const typename E::raw*>(g);
+  auto* sp = reinterpret_cast<typename E::raw*>(scaled);
+
+  int live = 0;  // 1 + the last row in which this lane saw a non-zero
+  for (int64_t p0 = wave_global; p0 < npairs;
+       p0 += kScaleInFlight * nwaves) {
+    Pack p[kScaleInFlight];
+    float s[kScaleInFlight];
+    int64_t row[kScaleInFlight], f0[kScaleInFlight];
+    bool on[kScaleInFlight];
+    // every load is issued, none behind a branch: a pair past the end or a
+    // lane past the row reads the last valid place instead and stores nothing
+#pragma unroll
+    for (int j = 0; j < kScaleInFlight; ++j) {
+      const int64_t pair = p0 + j * nwaves;
+      const int64_t pc = min(pair, npairs - 1);
+      row[j] = pc / nchunks;
+      f0[j] = pc % nchunks * (kWave * VEC) + lane * VEC;
+      on[j] = pair < npairs && f0[j] < F;
+      p[j] = *reinterpret_cast<const Pack*>(gp + row[j] * g_stride +
+                                            min(f0[j], F - VEC));
+      s[j] = E::scale(inv[row[j]]);
+    }
+#pragma unroll
+    for (int j = 0; j < kScaleInFlight; ++j) {
+      if (!on[j]) continue;
+      bool nz = false;
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) {
+        p[j].v[k] = E::mul(p[j].v[k], s[j]);
+        nz |= E::nonzero(p[j].v[k]);
+      }
+      *reinterpret_cast<Pack*>(sp + row[j] * F + f0[j]) = p[j];
+      if (nz) live = max(live, static_cast<int>(row[j]) + 1);
+    }
+  }
+  if (live > 0) atomicMax(&blk_live, live);
+  __syncthreads();
+  if (threadIdx.x == 0 && blk_live > 0) atomicMax(n_live, blk_live);
+}
+
 }  // namespace
+
+void scale_rows_live_hip(torch::Tensor g, torch::Tensor inv,
+                         torch::Tensor scaled, torch::Tensor n_live) {
+  TORCH_CHECK(g.is_cuda() && g.dim() == 2 && scaled.is_cuda() &&
+              inv.is_cuda() && n_live.is_cuda());
+  const bool bf16 = g.scalar_type() == torch::kBFloat16;
+  TORCH_CHECK(bf16 || g.scalar_type() == torch::kFloat,
+              "scale_rows_live: fp32 or bf16 only");
+  const int64_t N = g.size(0);
+  const int64_t F = g.size(1);
+  TORCH_CHECK(N < (int64_t{1} << 31) - 1, "scale_rows_live: int32 row count");
+  TORCH_CHECK(N <= 1 || F <= 1 || g.stride(1) == 1,
+              "scale_rows_live: unit column stride");
+  TORCH_CHECK(scaled.scalar_type() == g.scalar_type() &&
+              scaled.is_contiguous() && scaled.size(0) == N &&
+              scaled.size(1) == F);
+  TORCH_CHECK(inv.scalar_type() == torch::kFloat && inv.is_contiguous() &&
+              inv.numel() == N);
+  TORCH_CHECK(n_live.scalar_type() == torch::kInt && n_live.numel() == 1);
+  auto stream = current_stream();
+  HIP_CHECK(hipMemsetAsync(n_live.data_ptr(), 0, sizeof(int32_t), stream));
+  if (N == 0 || F == 0) return;
+  const int64_t g_stride = N > 1 ? g.stride(0) : F;
+  // widest move (16 B at most) that F, the row stride and both base
+  // addresses are multiples of
+  const int64_t elem = bf16 ? 2 : 4;
+  int vec = static_cast<int>(16 / elem);
+  while (vec > 1 &&
+         (F % vec || g_stride % vec || !aligned_to(g.data_ptr(), vec * elem) ||
+          !aligned_to(scaled.data_ptr(), vec * elem)))
+    vec >>= 1;
+  constexpr int threads = 256;  // 4 whole waves
+  const int64_t nchunks = (F + kWave * vec - 1) / (kWave * vec);
+  // one resident set of blocks, the grid-stride loop covers the rest: every
+  // block ends in an atomic on the one counter, and with 8192 blocks those
+  // cost a quarter of the pass (profiles/README.md, "Dead gradient rows")
+  const int64_t blocks = std::min<int64_t>(
+      (N * nchunks + threads / kWave * kScaleInFlight - 1) /
+          (threads / kWave * kScaleInFlight),
+      2048);
+  auto launch = [&](auto tptr, auto kern) {
+    using TP = decltype(tptr);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), 0, stream,
+                       reinterpret_cast<const TP>(g.data_ptr()),
+                       inv.data_ptr<float>(),
+                       reinterpret_cast<TP>(scaled.data_ptr()),
+                       n_live.data_ptr<int32_t>(), N, F, g_stride, nchunks);
+  };
+  dispatch_vec(vec, [&](auto v) {
+    if (bf16)
+      launch((__hip_bfloat16*)nullptr,
+             HIP_KERNEL_NAME(scale_rows_live_kernel<__hip_bfloat16, v.value>));
+    else if constexpr (v.value <= 4)
+      launch((float*)nullptr,
+             HIP_KERNEL_NAME(scale_rows_live_kernel<float, v.value>));
+  });
+  check_launch();
+}
 
 void dropout_fwd_hip(torch::Tensor x, torch::Tensor y, torch::Tensor mask,
                      double p, int64_t seed) {

@@ -59,7 +59,14 @@ __device__ __forceinline__ void st(__hip_bfloat16* p, float v) {
 // hides the gather latency (profiles/README.md, negative results).
 // HAS_SRC_SCALE fuses a per-source-row scale (the transpose/backward SpMM's
 // D^{-1} pre-scale) into the gather.
-template <typename T, int VEC, bool HAS_SRC_SCALE>
+//
+// HAS_LIVE (the last layer's backward; docs/DESIGN.md, "Dead gradient rows"):
+// the rows of feat from *n_live on are all zero. Every gathered id u becomes
+// min(u, *n_live) — one scalar min per edge, the ids being wave-uniform — so
+// the loads of dead rows all hit the one zero row n_live, which stays in
+// L1/L2, and never reach HBM. Same loads, same order, same adds: the result
+// is bitwise that of the plain kernel.
+template <typename T, int VEC, bool HAS_SRC_SCALE, bool HAS_LIVE>
 __global__ void spmm_csr_kernel(const int64_t* __restrict__ indptr,
                                 const int32_t* __restrict__ indices,
                                 const T* __restrict__ feat,
@@ -67,7 +74,18 @@ __global__ void spmm_csr_kernel(const int64_t* __restrict__ indptr,
                                 const float* __restrict__ src_scale,
                                 const int32_t* __restrict__ row_order,
                                 T* __restrict__ out, int64_t num_rows,
-                                int64_t F, int64_t nchunks) {
+                                int64_t F, int64_t nchunks,
+                                const int32_t* __restrict__ n_live) {
+  static_assert(!(HAS_SRC_SCALE && HAS_LIVE),
+                "the redirect would also redirect the scale's index");
+  // read once per wave (a scalar load); max() only keeps a corrupt count
+  // from forming a negative row address
+  int32_t live = 0;
+  if constexpr (HAS_LIVE) live = max(*n_live, 0);
+  // the id as gathered: itself, or the zero row for a dead one
+  auto node = [&](int32_t u) -> int64_t {
+    return HAS_LIVE ? min(u, live) : u;
+  };
   // the wave index in a scalar register: row, edge cursor and node ids are
   // then wave-uniform for the compiler too (spmm_packed.hip has the convention)
   const int wave_in_block =
@@ -103,7 +121,7 @@ __global__ void spmm_csr_kernel(const int64_t* __restrict__ indptr,
       // 1 index load + 4 row gathers instead of 8 instructions (the gather
       // path is instruction-rate-limited at small F; profiles/README.md).
       for (; e < e_end && (e & 3); ++e) {
-        const int64_t u = indices[e];
+        const int64_t u = node(indices[e]);
         const float s = HAS_SRC_SCALE ? src_scale[u] : 1.f;
 #pragma unroll
         for (int k = 0; k < VEC; ++k)
@@ -111,10 +129,10 @@ __global__ void spmm_csr_kernel(const int64_t* __restrict__ indptr,
       }
       for (; e + 4 <= e_end; e += 4) {
         const int32x4 uu = *reinterpret_cast<const int32x4*>(indices + e);
-        const int64_t u0 = uu[0];
-        const int64_t u1 = uu[1];
-        const int64_t u2 = uu[2];
-        const int64_t u3 = uu[3];
+        const int64_t u0 = node(uu[0]);
+        const int64_t u1 = node(uu[1]);
+        const int64_t u2 = node(uu[2]);
+        const int64_t u3 = node(uu[3]);
         float s0 = 1.f, s1 = 1.f, s2 = 1.f, s3 = 1.f;
         if (HAS_SRC_SCALE) {
           s0 = src_scale[u0];
@@ -142,7 +160,7 @@ __global__ void spmm_csr_kernel(const int64_t* __restrict__ indptr,
         }
       }
       for (; e < e_end; ++e) {
-        const int64_t u = indices[e];
+        const int64_t u = node(indices[e]);
         const float s = HAS_SRC_SCALE ? src_scale[u] : 1.f;
 #pragma unroll
         for (int k = 0; k < VEC; ++k)
@@ -154,7 +172,7 @@ __global__ void spmm_csr_kernel(const int64_t* __restrict__ indptr,
     } else {
       // ragged tail chunk: scalar guarded
       for (; e < e_end; ++e) {
-        const int64_t u = indices[e];
+        const int64_t u = node(indices[e]);
         const float s = HAS_SRC_SCALE ? src_scale[u] : 1.f;
         for (int k = 0; k < VEC && f0 + k < F; ++k)
           acc[k] += s * to_f32(feat[u * F + f0 + k]);
@@ -169,8 +187,9 @@ __global__ void spmm_csr_kernel(const int64_t* __restrict__ indptr,
 template <typename T, int VEC>
 void launch_spmm(const int64_t* indptr, const int32_t* indices,
                  const T* feat, const float* dst_scale,
-                 const float* src_scale, const int32_t* row_order, T* out,
-                 int64_t num_rows, int64_t F, hipStream_t stream) {
+                 const float* src_scale, const int32_t* row_order,
+                 const int32_t* n_live, T* out, int64_t num_rows, int64_t F,
+                 hipStream_t stream) {
   const int64_t nchunks = (F + kWave * VEC - 1) / (kWave * VEC);
   constexpr int threads = 256;  // 4 whole waves: the kernel keeps the
   static_assert(threads % kWave == 0);  // wave index in a scalar register
@@ -178,12 +197,14 @@ void launch_spmm(const int64_t* indptr, const int32_t* indices,
   auto launch = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), 0, stream, indptr,
                        indices, feat, dst_scale, src_scale, row_order, out,
-                       num_rows, F, nchunks);
+                       num_rows, F, nchunks, n_live);
   };
-  if (src_scale)
-    launch(HIP_KERNEL_NAME(spmm_csr_kernel<T, VEC, true>));
+  if (n_live)  // spmm_csr_hip refuses it together with src_scale
+    launch(HIP_KERNEL_NAME(spmm_csr_kernel<T, VEC, false, true>));
+  else if (src_scale)
+    launch(HIP_KERNEL_NAME(spmm_csr_kernel<T, VEC, true, false>));
   else
-    launch(HIP_KERNEL_NAME(spmm_csr_kernel<T, VEC, false>));
+    launch(HIP_KERNEL_NAME(spmm_csr_kernel<T, VEC, false, false>));
   check_launch();
 }
 
@@ -327,14 +348,14 @@ int pick_vec(int64_t F, int64_t num_rows, int64_t elem_size = 4) {
 template <typename T>
 void spmm_dispatch(torch::Tensor& indptr, torch::Tensor& indices,
                    torch::Tensor& feat, const float* dsp, const float* ssp,
-                   const int32_t* rop, torch::Tensor& out, int64_t num_rows,
-                   int64_t F, int vec, hipStream_t stream) {
+                   const int32_t* rop, const int32_t* nlp, torch::Tensor& out,
+                   int64_t num_rows, int64_t F, int vec, hipStream_t stream) {
   const T* fp = reinterpret_cast<const T*>(feat.data_ptr());
   T* op = reinterpret_cast<T*>(out.data_ptr());
   const int64_t* ip = indptr.data_ptr<int64_t>();
   const int32_t* xp = indices.data_ptr<int32_t>();
   dispatch_vec(vec, [&](auto v) {
-    launch_spmm<T, v.value>(ip, xp, fp, dsp, ssp, rop, op, num_rows, F,
+    launch_spmm<T, v.value>(ip, xp, fp, dsp, ssp, rop, nlp, op, num_rows, F,
                             stream);
   });
 }
@@ -342,7 +363,7 @@ void spmm_dispatch(torch::Tensor& indptr, torch::Tensor& indices,
 void spmm_csr_hip(torch::Tensor indptr, torch::Tensor indices,
                   torch::Tensor feat, torch::Tensor dst_scale,
                   torch::Tensor src_scale, torch::Tensor row_order,
-                  torch::Tensor out) {
+                  torch::Tensor out, torch::Tensor n_live) {
   TORCH_CHECK(feat.is_cuda() && out.is_cuda(), "spmm_csr_hip: device tensors");
   const bool bf16 = feat.scalar_type() == torch::kBFloat16;
   TORCH_CHECK(bf16 || feat.scalar_type() == torch::kFloat,
@@ -373,14 +394,24 @@ void spmm_csr_hip(torch::Tensor indptr, torch::Tensor indices,
                 row_order.scalar_type() == torch::kInt);
     rop = row_order.data_ptr<int32_t>();
   }
+  const int32_t* nlp = nullptr;
+  if (n_live.defined() && n_live.numel() > 0) {
+    TORCH_CHECK(n_live.is_cuda() && n_live.numel() == 1 &&
+                    n_live.scalar_type() == torch::kInt,
+                "spmm: n_live is one int32 in device memory");
+    TORCH_CHECK(ssp == nullptr,
+                "spmm: n_live and src_scale do not combine (the redirect "
+                "would pick another row's scale)");
+    nlp = n_live.data_ptr<int32_t>();
+  }
   auto stream = current_stream();
   const int vec = pick_vec(F, num_rows, bf16 ? 2 : 4);
   if (bf16)
-    spmm_dispatch<__hip_bfloat16>(indptr, indices, feat, dsp, ssp, rop, out,
-                                  num_rows, F, vec, stream);
+    spmm_dispatch<__hip_bfloat16>(indptr, indices, feat, dsp, ssp, rop, nlp,
+                                  out, num_rows, F, vec, stream);
   else
-    spmm_dispatch<float>(indptr, indices, feat, dsp, ssp, rop, out, num_rows,
-                         F, vec, stream);
+    spmm_dispatch<float>(indptr, indices, feat, dsp, ssp, rop, nlp, out,
+                         num_rows, F, vec, stream);
 }
 
 template <typename T, bool SCATTER_ADD>

@@ -56,8 +56,15 @@ def _tune_row_order(csr: CSR, feat, s, ss) -> bool:
 
 def spmm(csr: CSR, feat: torch.Tensor,
          scale: Optional[torch.Tensor] = None,
-         src_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """out[r,:] = scale[r] * sum_{u in N(r)} src_scale[u] * feat[u,:]."""
+         src_scale: Optional[torch.Tensor] = None,
+         n_live: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[r,:] = scale[r] * sum_{u in N(r)} src_scale[u] * feat[u,:].
+
+    n_live (GPU, not with src_scale): one int32 in device memory, the
+    caller's promise that the rows of feat from n_live on are all zero (as
+    `scale_rows_live` counts them). The kernel then gathers the one zero row
+    n_live in their place, which stays in cache; the result is bitwise the
+    same (docs/DESIGN.md, "Dead gradient rows")."""
     if feat.shape[0] < csr.num_cols:
         raise ValueError(
             f"spmm: feat has {feat.shape[0]} rows but the graph references "
@@ -91,8 +98,20 @@ def spmm(csr: CSR, feat: torch.Tensor,
             cache[feat.shape[1]] = use_lpt
         if not use_lpt:
             ro = torch.Tensor()
+    if n_live is None:
+        return native().spmm(csr.indptr, csr.indices, feat, s, ss,
+                             ro, csr.num_rows)
     return native().spmm(csr.indptr, csr.indices, feat, s, ss,
-                         ro, csr.num_rows)
+                         ro, csr.num_rows, n_live)
+
+
+def scale_rows_live(g: torch.Tensor, inv: torch.Tensor):
+    """(g * inv per row, n_live) in one GPU pass: n_live is an int32 [1]
+    device tensor holding 1 + the index of the last row of the product with
+    a non-zero in it (0 if there is none; both zeros are zero, NaN and +-Inf
+    are not). The product is bitwise `g * inv.unsqueeze(1).to(g.dtype)`.
+    Nothing is read back to the host."""
+    return native().scale_rows_live(g, inv)
 
 
 def packed_row_layout(F: int):
@@ -226,8 +245,8 @@ class _SpmmMean(torch.autograd.Function):
         ctx.graph = graph
         ctx.save_for_backward(inv_deg)
         # the forward input is dropout's output (half zeros, three quarters
-        # after a ReLU): gather it packed. The backward's input is a dense
-        # gradient and stays on the dense kernel.
+        # after a ReLU): gather it packed. The backward's input is a gradient,
+        # dense in the rows that have one, and stays on the dense kernel.
         if _spmm_packed_route(feat):
             return spmm_packed(graph.csr, feat, inv_deg)
         return spmm(graph.csr, feat, inv_deg)
@@ -243,9 +262,21 @@ class _SpmmMean(torch.autograd.Function):
         # measured +1 ms/call for pre-scale) want the multiply, sparse
         # wide ones (yelp: nnz 14M << numel 367M) want the gather
         if g.csc.nnz > grad_out.numel():
-            grad_feat = spmm(
-                g.csc,
-                grad_out * inv_deg.unsqueeze(1).to(grad_out.dtype), None)
+            if grad_out.is_cuda:
+                # the multiply also finds where the gradient's all-zero
+                # tail starts: the loss covers the train nodes, which are
+                # numbered first, so under the last layer every later row
+                # is zero, and the gather keeps those out of HBM. Other
+                # layers find n_live == rows and nothing changes.
+                # PIPEGCN_SPMM_LIVE=0 withholds the count.
+                scaled, n_live = scale_rows_live(grad_out, inv_deg)
+                if os.environ.get("PIPEGCN_SPMM_LIVE", "1") == "0":
+                    n_live = None
+                grad_feat = spmm(g.csc, scaled, None, n_live=n_live)
+            else:
+                grad_feat = spmm(
+                    g.csc,
+                    grad_out * inv_deg.unsqueeze(1).to(grad_out.dtype), None)
         else:
             grad_feat = spmm(g.csc, grad_out.contiguous(), None,
                              src_scale=inv_deg)

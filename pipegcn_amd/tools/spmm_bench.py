@@ -10,9 +10,16 @@ dense kernel on features of which only that share is non-zero (what dropout
 and ReLU leave): dense SpMM, pack pass and packed SpMM alternate in the same
 rounds, and the two outputs must be bitwise equal.
 
+With --dead-frac it compares the dense kernel with and without the dead-row
+redirect (the last layer's backward) on features whose trailing share of rows
+is all zero: the pre-scale pass that counts the live rows, the plain kernel
+and the redirecting one alternate in the same rounds, and the two outputs
+must be bitwise equal.
+
 Usage (on a GPU box):
     python -m pipegcn_amd.tools.spmm_bench [--f 602 256] [--rounds 5]
     python -m pipegcn_amd.tools.spmm_bench --f 256 --density 0.25 0.5 1.0
+    python -m pipegcn_amd.tools.spmm_bench --f 256 --dead-frac 0 0.34 0.92
 """
 import argparse
 import os
@@ -88,6 +95,69 @@ def density_table(hg, E, inv, widths, densities, rounds, iters):
             del feat, packed
 
 
+def dead_rows_table(hg, inv, widths, fracs, dtype, rounds, iters):
+    """The dense kernel without and with the dead-row redirect on features
+    whose last `frac` of the rows is zero, alternating in the same rounds
+    with the eager row scale and the fused scale-and-count pass that feeds
+    the redirect. Prints best ms and checks the two outputs bitwise."""
+    from pipegcn_amd import native
+
+    n = hg.num_all
+    csr = hg.csr
+    ro = csr.row_order
+    none = torch.Tensor()
+    print("    F  dead | n_live  | eager scale ms | scale+count ms |"
+          " plain ms | redirect ms | redirect vs plain")
+    for F in widths:
+        for frac in fracs:
+            g = torch.Generator(device="cuda").manual_seed(F)
+            feat = torch.randn(n, F, device="cuda", generator=g).to(dtype)
+            feat[n - int(round(frac * n)):] = 0
+            scaled, n_live = native().scale_rows_live(feat, inv)
+            assert torch.equal(
+                scaled.view(torch.int16 if dtype == torch.bfloat16
+                            else torch.int32),
+                (feat * inv.unsqueeze(1).to(dtype)).view(
+                    torch.int16 if dtype == torch.bfloat16
+                    else torch.int32)), \
+                f"F={F}: fused row scale differs from the eager product"
+
+            def eager():
+                return feat * inv.unsqueeze(1).to(dtype)
+
+            def fused():
+                return native().scale_rows_live(feat, inv)
+
+            def plain():
+                return native().spmm(csr.indptr, csr.indices, scaled, none,
+                                     none, ro, csr.num_rows)
+
+            def redirect():
+                return native().spmm(csr.indptr, csr.indices, scaled, none,
+                                     none, ro, csr.num_rows, n_live)
+
+            assert torch.equal(plain().view(torch.uint8),
+                               redirect().view(torch.uint8)), \
+                f"F={F} dead={frac}: redirecting SpMM differs from plain"
+            best = {}
+            for _ in range(rounds):
+                for name, fn in (("eager", eager), ("fused", fused),
+                                 ("plain", plain), ("redirect", redirect)):
+                    fn()
+                    torch.cuda.synchronize()
+                    t0 = time.time()
+                    for _ in range(iters):
+                        fn()
+                    torch.cuda.synchronize()
+                    t = (time.time() - t0) / iters * 1e3
+                    best[name] = min(best.get(name, t), t)
+            print(f"{F:5d}  {frac:4.2f} | {int(n_live):7d} |"
+                  f" {best['eager']:14.3f} | {best['fused']:14.3f} |"
+                  f" {best['plain']:8.2f} | {best['redirect']:11.2f} |"
+                  f" {best['redirect'] / best['plain']:.3f}x", flush=True)
+            del feat, scaled
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--f", type=int, nargs="+", default=[602, 256])
@@ -102,6 +172,12 @@ def main():
                          "each share D of non-zero features, time the "
                          "dense SpMM, the pack pass and the packed SpMM "
                          "(fp32)")
+    ap.add_argument("--dead-frac", type=float, nargs="+", default=None,
+                    metavar="S",
+                    help="instead of the lane-width A/B: for each F and "
+                         "each share S of trailing all-zero rows, time the "
+                         "dense SpMM without and with the dead-row redirect, "
+                         "and the row scale that counts the live rows")
     args = ap.parse_args()
 
     from pipegcn_amd import ops
@@ -116,6 +192,12 @@ def main():
             raise SystemExit("--density: the packed path is fp32 only")
         density_table(hg, E, inv, args.f, args.density, args.rounds,
                       args.iters)
+        return
+
+    if args.dead_frac:
+        dead_rows_table(hg, inv, args.f, args.dead_frac,
+                        torch.bfloat16 if args.dtype == "bf16"
+                        else torch.float32, args.rounds, args.iters)
         return
 
     elem = 2 if args.dtype == "bf16" else 4
