@@ -40,6 +40,13 @@ def create_parser(argv=None):
                              "probability in [0, 1) of dropping an edge's "
                              "attention coefficient, per head, in training "
                              "(--model gat, gatv2)")
+    parser.add_argument("--aggregator", choices=["mean", "pool"],
+                        default="mean",
+                        help="neighbourhood aggregator of the GraphSAGE "
+                             "layers: mean, or max-pooling over projected "
+                             "and rectified neighbours (--model graphsage; "
+                             "pool does not combine with --use-pp; "
+                             "extension over the reference)")
     parser.add_argument("--norm", choices=["layer", "batch", "none"],
                         default="layer", help="normalization method")
     parser.add_argument("--weight-decay", "--weight_decay", type=float,

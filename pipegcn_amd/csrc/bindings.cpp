@@ -32,6 +32,47 @@ static torch::Tensor spmm(torch::Tensor indptr, torch::Tensor indices,
   return spmm_cpu(indptr, indices, feat, dst_scale, src_scale, num_rows);
 }
 
+// -> [out] or, with_arg, [out, arg]
+static std::vector<torch::Tensor> spmm_max(torch::Tensor indptr,
+                                           torch::Tensor indices,
+                                           torch::Tensor z,
+                                           torch::Tensor row_order,
+                                           int64_t num_rows, int64_t num_cols,
+                                           bool with_arg) {
+  TORCH_CHECK(indptr.numel() == num_rows + 1,
+              "spmm_max: indptr must hold num_rows + 1 entries");
+  if (z.is_cuda())
+    return spmm_max_fwd_hip(indptr, indices, z, row_order, num_cols, with_arg);
+  TORCH_CHECK(z.dim() == 2 && z.size(0) >= num_cols, "spmm_max: z has ",
+              z.size(0), " rows but the graph references ", num_cols);
+  if (z.scalar_type() == torch::kBFloat16) {
+    // the CPU tier compares in fp32; the maximum is one of the inputs, so
+    // the way back to bf16 is exact
+    auto res = max_aggregate_cpu(indptr, indices, z.to(torch::kFloat),
+                                 num_rows, with_arg);
+    res[0] = res[0].to(torch::kBFloat16);
+    return res;
+  }
+  return max_aggregate_cpu(indptr, indices, z, num_rows, with_arg);
+}
+
+// GPU: gather over the simple CSC (rows = the num_src sources). CPU: a
+// scatter of g by arg, which needs no graph (pass empty tensors).
+static torch::Tensor spmm_max_bwd(torch::Tensor indptr, torch::Tensor indices,
+                                  torch::Tensor g, torch::Tensor arg,
+                                  torch::Tensor row_order, int64_t num_src,
+                                  int64_t num_cols) {
+  if (g.is_cuda()) {
+    TORCH_CHECK(indptr.numel() == num_src + 1,
+                "spmm_max_bwd: indptr must hold num_src + 1 entries");
+    return spmm_max_bwd_hip(indptr, indices, g, arg, row_order, num_cols);
+  }
+  if (g.scalar_type() == torch::kBFloat16)
+    return max_aggregate_bwd_cpu(g.to(torch::kFloat), arg, num_src)
+        .to(torch::kBFloat16);
+  return max_aggregate_bwd_cpu(g, arg, num_src);
+}
+
 // GPU-only (ops._SpmmMean.backward multiplies eagerly on the CPU)
 static std::vector<torch::Tensor> scale_rows_live(torch::Tensor g,
                                                   torch::Tensor inv) {
@@ -178,6 +219,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("indptr"), py::arg("indices"), py::arg("feat"),
         py::arg("dst_scale"), py::arg("src_scale"), py::arg("row_order"),
         py::arg("num_rows"), py::arg("n_live") = py::none());
+  m.def("csr_simple", &csr_simple,
+        "CSR without repeated entries in a row -> (indptr, indices, removed)");
+  m.def("spmm_max", &spmm_max,
+        "max aggregation over the CSR -> [out] or [out, arg]",
+        py::arg("indptr"), py::arg("indices"), py::arg("z"),
+        py::arg("row_order"), py::arg("num_rows"), py::arg("num_cols"),
+        py::arg("with_arg"));
+  m.def("spmm_max_bwd", &spmm_max_bwd,
+        "grad_z of the max aggregation (GPU: over the simple CSC)",
+        py::arg("indptr"), py::arg("indices"), py::arg("g"), py::arg("arg"),
+        py::arg("row_order"), py::arg("num_src"), py::arg("num_cols"));
   m.def("scale_rows_live", &scale_rows_live,
         "g * inv per row -> (scaled, n_live = 1 + last non-zero row, int32)");
   m.def("pack_rows", &pack_rows,

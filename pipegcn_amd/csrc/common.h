@@ -41,9 +41,53 @@ torch::Tensor spmm_cpu(torch::Tensor indptr, torch::Tensor indices,
                        torch::Tensor feat, torch::Tensor dst_scale,
                        torch::Tensor src_scale, int64_t num_rows);
 
+// Max aggregation on the CPU (the contract: docs/DESIGN.md, "Max
+// aggregation"). out[r,c] = max over the edges of row r of z[indices[e],c],
+// arg[r,c] = the source id of the first edge, in stored order, that attains
+// it (initialised from the first edge, updated on strict >); rows without
+// edges give 0 and -1. z fp32 [num_src, F]. -> {out} or, with_arg, {out, arg}.
+std::vector<torch::Tensor> max_aggregate_cpu(torch::Tensor indptr,
+                                             torch::Tensor indices,
+                                             torch::Tensor z, int64_t num_rows,
+                                             bool with_arg);
+// grad_z[u,c] = sum of g[r,c] over the rows r with arg[r,c] == u: a scatter
+// of g by arg, serial over r inside each column block (deterministic, every
+// destination counted once). g fp32 [rows, F], arg int32 [rows, F] with
+// entries in [-1, num_src). -> fp32 [num_src, F].
+torch::Tensor max_aggregate_bwd_cpu(torch::Tensor g, torch::Tensor arg,
+                                    int64_t num_src);
+
+// The CSR with each row's repeated entries removed (rows come out sorted),
+// parallel over rows. -> {indptr, indices, removed}: removed is a bool scalar
+// tensor; when it is false the first two are the inputs themselves.
+std::vector<torch::Tensor> csr_simple(torch::Tensor indptr,
+                                      torch::Tensor indices);
+
 // ---------------------------------------------------------------------------
 // HIP kernel launchers (hip/*.hip) — gfx950 only.
 // ---------------------------------------------------------------------------
+
+// Elements per lane access of the wave-per-(row, chunk) gathers for rows of F
+// elements of elem_size bytes: 8-byte accesses first (16-byte first from 2^20
+// rows on), PIPEGCN_SPMM_VEC overrides. Always divides F. (hip/kernels.hip)
+int pick_vec(int64_t F, int64_t num_rows, int64_t elem_size = 4);
+
+// Max aggregation (hip/spmm_max.hip): max_aggregate_cpu's contract for fp32 or
+// bf16 z [>= num_cols, F]; comparison in fp32, the result is one of the
+// inputs. -> {out} or, with_arg, {out, arg int32 [num_rows, F]}.
+std::vector<torch::Tensor> spmm_max_fwd_hip(torch::Tensor indptr,
+                                            torch::Tensor indices,
+                                            torch::Tensor z,
+                                            torch::Tensor row_order,
+                                            int64_t num_cols, bool with_arg);
+// Its backward; indptr/indices/row_order are a CSC WITHOUT repeated entries
+// (rows = sources u, columns = destinations r < num_cols): grad_z[u,c] = sum
+// over the entries r of row u of g[r,c] where arg[r,c] == u, fp32 accumulate.
+// g fp32 or bf16 [>= num_cols, F], arg int32 of the same shape.
+// -> [num_rows, F] in g's dtype.
+torch::Tensor spmm_max_bwd_hip(torch::Tensor indptr, torch::Tensor indices,
+                               torch::Tensor g, torch::Tensor arg,
+                               torch::Tensor row_order, int64_t num_cols);
 
 // out[r,:] = scale[r] * sum_{e in [indptr[r], indptr[r+1])} feat[indices[e],:]
 // All tensors on device. feat fp32 [num_src, F], out fp32 [num_rows, F].

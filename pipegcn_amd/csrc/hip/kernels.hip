@@ -317,7 +317,10 @@ __global__ void colsum_partial_kernel(const float* __restrict__ x,
   }
 }
 
-int pick_vec(int64_t F, int64_t num_rows, int64_t elem_size = 4) {
+}  // namespace
+
+// declared in common.h: spmm_max.hip starts from the same preference
+int pick_vec(int64_t F, int64_t num_rows, int64_t elem_size) {
   // With LPT row scheduling handling load balance, width is a pure
   // throughput choice. Measured on MI355X (profiles/README.md): 8 B lane
   // loads win at F=256 fp32 (VEC2 15.4 ms vs VEC1 15.7 / VEC4 16.0) and
@@ -342,8 +345,6 @@ int pick_vec(int64_t F, int64_t num_rows, int64_t elem_size = 4) {
   }
   return 1;
 }
-
-}  // namespace
 
 template <typename T>
 void spmm_dispatch(torch::Tensor& indptr, torch::Tensor& indices,

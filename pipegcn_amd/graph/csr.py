@@ -73,6 +73,31 @@ class HaloGraph:
         return HaloGraph(self.csr.to(device), self.csc.to(device),
                          self.num_in, self.num_all)
 
+    def csc_simple(self) -> CSR:
+        """The CSC with each row's repeated entries removed: what the max
+        aggregation's backward walks (docs/DESIGN.md, "Max aggregation").
+        `build_csr` keeps parallel edges, and a destination must match its
+        arg-max once however many parallel edges lead to it.
+
+        Built on first use and cached on this object, with its own LPT
+        row_order, on the CSC's device. A graph without parallel edges gets
+        `self.csc` itself back, and no new memory. The order inside a row
+        may differ from the CSC's."""
+        cached = getattr(self, "_csc_simple", None)
+        if cached is None:
+            csc = self.csc
+            indptr, indices, removed = native().csr_simple(
+                csc.indptr.cpu(), csc.indices.cpu())
+            if not bool(removed):
+                cached = csc
+            else:
+                deg = indptr[1:] - indptr[:-1]
+                order = torch.argsort(deg, descending=True).to(torch.int32)
+                cached = CSR(indptr, indices, csc.num_rows, csc.num_cols,
+                             order).to(csc.indptr.device)
+            self._csc_simple = cached
+        return cached
+
     @staticmethod
     def from_edges(u: torch.Tensor, v: torch.Tensor, num_in: int,
                    num_all: int) -> "HaloGraph":

@@ -9,7 +9,9 @@ HaloGraph/FullGraph CSR structures and hand-written gfx950 SpMM:
  - use_pp first layer collapses to one GEMM on [feat ‖ mean_agg]
    (layer.py:41-42);
  - eval path: full homogeneous graph, degrees from the graph (layer.py:52-62);
- - init: uniform ±1/sqrt(fan_in) (layer.py:24-36).
+ - init: uniform ±1/sqrt(fan_in) (layer.py:24-36);
+ - `aggregator="pool"`: GraphSAGE's max-pooling aggregator (SAGEPoolLayer),
+   an extension over the reference, which has the mean only.
 """
 from __future__ import annotations
 
@@ -68,6 +70,49 @@ class GraphSAGELayer(nn.Module):
         if self.use_pp:
             return self.linear(torch.cat((feat, ah), dim=1))
         return self.linear1(feat) + self.linear2(ah)
+
+
+class SAGEPoolLayer(nn.Module):
+    """GraphSAGE's max-pooling aggregator: every neighbour is projected and
+    rectified, the element-wise maximum over the neighbourhood joins the
+    node's own row:
+
+        z = relu(linear_pool(h))          on ALL local rows (inner + halo)
+        m[v] = max over u in N(v) of z[u]
+        out = linear1(h[:num_dst]) + linear2(m)
+
+    `ops.spmm_max` is the aggregation (csrc/hip/spmm_max.hip). The halo
+    exchange carries h at the layer's input width, as for the mean layer.
+    """
+
+    def __init__(self, in_feats, out_feats, bias=True):
+        super().__init__()
+        self.linear_pool = nn.Linear(in_feats, in_feats, bias=True)
+        self.linear1 = nn.Linear(in_feats, out_feats, bias=bias)
+        self.linear2 = nn.Linear(in_feats, out_feats, bias=bias)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for lin in (self.linear_pool, self.linear1, self.linear2):
+            stdv = 1.0 / math.sqrt(lin.weight.size(1))
+            lin.weight.data.uniform_(-stdv, stdv)
+            if lin.bias is not None:
+                lin.bias.data.uniform_(-stdv, stdv)
+
+    def forward(self, graph, feat, in_deg=None):
+        z = torch.relu(ops.linear(feat, self.linear_pool))
+        if self.training:
+            assert isinstance(graph, HaloGraph)
+            m = ops.spmm_max(graph, z)
+            x1 = feat[: graph.num_in]
+            if feat.is_cuda:
+                return ops.sage_dual_linear(x1, m, self.linear1,
+                                            self.linear2)
+            return self.linear1(x1) + self.linear2(m)
+        # eval: full homogeneous graph, every node is a destination
+        assert isinstance(graph, FullGraph)
+        m = ops.spmm_max_csr(graph.csr, z)
+        return self.linear1(feat) + self.linear2(m)
 
 
 class GNNBase(nn.Module):
@@ -149,14 +194,29 @@ class GNNBase(nn.Module):
         return self.activation(h)
 
 
+AGGREGATORS = ("mean", "pool")
+
+
 class GraphSAGE(GNNBase):
     def __init__(self, layer_size, activation, use_pp, dropout=0.5,
-                 norm="layer", train_size=None, n_linear=0):
+                 norm="layer", train_size=None, n_linear=0,
+                 aggregator="mean"):
+        if aggregator not in AGGREGATORS:
+            raise ValueError(f"unknown aggregator {aggregator!r}: one of "
+                             f"{', '.join(AGGREGATORS)}")
+        if use_pp and aggregator == "pool":
+            # layer 0's neighbourhood term passes through a learned
+            # projection, so there is nothing to precompute
+            raise NotImplementedError(
+                "--use-pp does not combine with --aggregator pool")
         super().__init__(layer_size, activation, dropout, norm, train_size,
-                         n_linear, use_pp=use_pp)
+                         n_linear, use_pp=use_pp, aggregator=aggregator)
         self.use_pp = use_pp
+        self.aggregator = aggregator
 
-    def make_conv(self, i, in_feats, out_feats, use_pp):
+    def make_conv(self, i, in_feats, out_feats, use_pp, aggregator):
+        if aggregator == "pool":
+            return SAGEPoolLayer(in_feats, out_feats)
         # use_pp applies to the first layer only: its input already holds
         # [feat ‖ mean_agg], precomputed once
         return GraphSAGELayer(in_feats, out_feats, use_pp=use_pp and i == 0)

@@ -293,6 +293,88 @@ def spmm_mean(graph: HaloGraph, feat: torch.Tensor,
     return _SpmmMean.apply(graph, feat, inv_deg)
 
 
+def _spmm_max_check(csr: CSR, z: torch.Tensor) -> None:
+    """Raised before any launch."""
+    if z.dim() != 2 or z.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("spmm_max: z must be a fp32 or bf16 [nodes, F] "
+                         f"tensor, got {tuple(z.shape)} {z.dtype}")
+    if z.shape[0] < csr.num_cols:
+        raise ValueError(
+            f"spmm_max: z has {z.shape[0]} rows but the graph references "
+            f"{csr.num_cols} source nodes (an under-sized z would be an "
+            "out-of-bounds GPU gather)")
+
+
+def _spmm_max_forward(csr: CSR, z: torch.Tensor, with_arg: bool):
+    """[out] or [out, arg] on z's device. Uses csr.row_order as given (no
+    lazy autotune here)."""
+    return native().spmm_max(csr.indptr, csr.indices, z.contiguous(),
+                             _row_order(csr), csr.num_rows, csr.num_cols,
+                             with_arg)
+
+
+class _SpmmMax(torch.autograd.Function):
+    """out[r] = max over u in N(r) of z[u], element-wise.
+
+    Saves the int32 arg-max [num_in, F] only, and only when z wants a
+    gradient. The backward adds g[r, c] into grad_z[arg[r, c], c]: on the
+    GPU as one gather pass over the graph's simple CSC (no atomics), on the
+    CPU as a scatter by arg.
+    """
+
+    @staticmethod
+    def forward(ctx, graph: HaloGraph, z: torch.Tensor):
+        need_grad = ctx.needs_input_grad[1]
+        out, *arg = _spmm_max_forward(graph.csr, z, need_grad)
+        if need_grad:
+            ctx.save_for_backward(*arg)
+        ctx.graph, ctx.num_src = graph, z.shape[0]
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (arg,) = ctx.saved_tensors
+        g = g.contiguous()
+        if not g.is_cuda:
+            none = torch.Tensor()
+            return None, native().spmm_max_bwd(none, none, g, arg, none,
+                                               ctx.num_src, g.shape[0])
+        csc = ctx.graph.csc_simple()
+        dz = native().spmm_max_bwd(csc.indptr, csc.indices, g, arg,
+                                   _row_order(csc), csc.num_rows,
+                                   csc.num_cols)
+        if dz.shape[0] < ctx.num_src:  # rows the graph never references
+            dz = torch.cat((dz, dz.new_zeros(ctx.num_src - dz.shape[0],
+                                             dz.shape[1])))
+        return None, dz
+
+
+def spmm_max(graph: HaloGraph, z: torch.Tensor) -> torch.Tensor:
+    """Differentiable max aggregation over the halo graph.
+
+    z [num_all, F], fp32 or bf16; returns out [num_in, F] with out[r, c] the
+    maximum of z[u, c] over the sources u of r, and 0 for a destination
+    without edges. The comparison is in fp32 and the result is one of the
+    inputs, so it is exact in both dtypes. The gradient of out[r, c] goes to
+    the source of the first edge of r, in CSR order, that attains the
+    maximum — once, however many parallel u -> r edges there are
+    (docs/DESIGN.md, "Max aggregation"). NaN inputs are unspecified.
+    """
+    _spmm_max_check(graph.csr, z)
+    return _SpmmMax.apply(graph, z)
+
+
+def spmm_max_csr(csr: CSR, z: torch.Tensor, with_arg: bool = False):
+    """Forward-only max aggregation over a plain CSR (full-graph eval over
+    FullGraph.csr). Returns out, or (out, arg) with the int32 arg-max
+    [num_rows, F]: the source id the maximum came from, -1 on rows without
+    edges."""
+    _spmm_max_check(csr, z)
+    with torch.no_grad():
+        res = _spmm_max_forward(csr, z, with_arg)
+    return (res[0], res[1]) if with_arg else res[0]
+
+
 def _gat_check(csr: CSR, z, el, er, num_heads: int) -> None:
     """Shape guards shared by both GAT paths; raised before any launch."""
     if num_heads < 1 or z.dim() != 2 or z.shape[1] % num_heads != 0:

@@ -16,10 +16,16 @@ is all zero: the pre-scale pass that counts the live rows, the plain kernel
 and the redirecting one alternate in the same rounds, and the two outputs
 must be bitwise equal.
 
+With --max it compares the max aggregation (csrc/hip/spmm_max.hip) with the
+mean SpMM on the same graph, fp32 and bf16: max forward with and without the
+arg-max output, max backward over the duplicate-free CSC, dense mean forward
+and its transpose alternate in the same rounds.
+
 Usage (on a GPU box):
     python -m pipegcn_amd.tools.spmm_bench [--f 602 256] [--rounds 5]
     python -m pipegcn_amd.tools.spmm_bench --f 256 --density 0.25 0.5 1.0
     python -m pipegcn_amd.tools.spmm_bench --f 256 --dead-frac 0 0.34 0.92
+    python -m pipegcn_amd.tools.spmm_bench --max
 """
 import argparse
 import os
@@ -158,6 +164,83 @@ def dead_rows_table(hg, inv, widths, fracs, dtype, rounds, iters):
             del feat, scaled
 
 
+def max_table(hg, E, widths, rounds, iters):
+    """The max aggregation against the mean SpMM at the same shape, fp32 and
+    bf16: max forward with arg, max forward without, max backward (over the
+    simple CSC), dense mean forward and its transpose, alternating in the
+    same rounds after warm-up. Prints best ms, the ratios and logical TB/s
+    computed from shapes: per edge the index and one gathered row (the max
+    backward: two, g at the element size and arg at 4 bytes), per output
+    element one store (the max forward with arg: two)."""
+    from pipegcn_amd import native
+
+    n = hg.num_all
+    csr, csc, simple = hg.csr, hg.csc, hg.csc_simple()
+    none = torch.Tensor()
+    print(f"simple CSC: {simple.nnz} of {csc.nnz} entries")
+    print("dtype     F | max fwd+arg | max fwd | max bwd | mean fwd | mean T |"
+          " fwd+arg/mean  fwd/mean  bwd/T | logical TB/s: fwd+arg  fwd  bwd"
+          "  mean fwd  mean T")
+    for dname, dtype, es in (("fp32", torch.float32, 4),
+                             ("bf16", torch.bfloat16, 2)):
+        for F in widths:
+            gen = torch.Generator(device="cuda").manual_seed(F)
+            z = torch.randn(n, F, device="cuda", generator=gen).to(dtype)
+            g = torch.randn(hg.num_in, F, device="cuda",
+                            generator=gen).to(dtype)
+            arg = native().spmm_max(csr.indptr, csr.indices, z, csr.row_order,
+                                    csr.num_rows, csr.num_cols, True)[1]
+            fns = {
+                "fwd_arg": lambda: native().spmm_max(
+                    csr.indptr, csr.indices, z, csr.row_order, csr.num_rows,
+                    csr.num_cols, True),
+                "fwd": lambda: native().spmm_max(
+                    csr.indptr, csr.indices, z, csr.row_order, csr.num_rows,
+                    csr.num_cols, False),
+                "bwd": lambda: native().spmm_max_bwd(
+                    simple.indptr, simple.indices, g, arg, simple.row_order,
+                    simple.num_rows, simple.num_cols),
+                "mean": lambda: native().spmm(
+                    csr.indptr, csr.indices, z, none, none, csr.row_order,
+                    csr.num_rows),
+                "mean_t": lambda: native().spmm(
+                    csc.indptr, csc.indices, g, none, none, csc.row_order,
+                    csc.num_rows),
+            }
+            for fn in fns.values():
+                fn()
+                fn()
+            best = {}
+            for _ in range(rounds):
+                for name, fn in fns.items():
+                    torch.cuda.synchronize()
+                    t0 = time.time()
+                    for _ in range(iters):
+                        fn()
+                    torch.cuda.synchronize()
+                    t = (time.time() - t0) / iters * 1e3
+                    best[name] = min(best.get(name, t), t)
+            rows_out = hg.num_in * F
+            logical = {
+                "fwd_arg": csr.nnz * (es * F + 4) + rows_out * (es + 4),
+                "fwd": csr.nnz * (es * F + 4) + rows_out * es,
+                "bwd": simple.nnz * ((es + 4) * F + 4) + n * F * es,
+                "mean": csr.nnz * (es * F + 4) + rows_out * es,
+                "mean_t": csc.nnz * (es * F + 4) + n * F * es,
+            }
+            tbs = {k: logical[k] / best[k] / 1e9 for k in best}
+            print(f"{dname} {F:6d} | {best['fwd_arg']:11.2f} |"
+                  f" {best['fwd']:7.2f} | {best['bwd']:7.2f} |"
+                  f" {best['mean']:8.2f} | {best['mean_t']:6.2f} |"
+                  f" {best['fwd_arg'] / best['mean']:12.3f}x"
+                  f" {best['fwd'] / best['mean']:8.3f}x"
+                  f" {best['bwd'] / best['mean_t']:5.3f}x |"
+                  f" {tbs['fwd_arg']:21.2f} {tbs['fwd']:5.2f}"
+                  f" {tbs['bwd']:5.2f} {tbs['mean']:8.2f}"
+                  f" {tbs['mean_t']:7.2f}", flush=True)
+            del z, g, arg
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--f", type=int, nargs="+", default=[602, 256])
@@ -178,6 +261,11 @@ def main():
                          "each share S of trailing all-zero rows, time the "
                          "dense SpMM without and with the dead-row redirect, "
                          "and the row scale that counts the live rows")
+    ap.add_argument("--max", action="store_true",
+                    help="instead of the lane-width A/B: the max "
+                         "aggregation (forward with and without arg, "
+                         "backward) against the mean SpMM and its transpose, "
+                         "fp32 and bf16, at --f (default 64 256 602)")
     args = ap.parse_args()
 
     from pipegcn_amd import ops
@@ -187,6 +275,10 @@ def main():
     deg = hg.csr.row_degrees().to("cuda").clamp(min=1)
     inv = (1.0 / deg).contiguous()
     print(f"graph: {n} nodes, {E} edges")
+    if args.max:
+        widths = args.f if args.f != ap.get_default("f") else [64, 256, 602]
+        max_table(hg, E, widths, args.rounds, args.iters)
+        return
     if args.density:
         if args.dtype != "fp32":
             raise SystemExit("--density: the packed path is fp32 only")

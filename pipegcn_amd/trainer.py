@@ -142,6 +142,10 @@ def precompute(rp: RuntimePartition, args) -> torch.Tensor:
     if args.model != "graphsage":
         raise NotImplementedError(
             "--use-pp supports graphsage only (reference parity)")
+    if getattr(args, "aggregator", "mean") == "pool":
+        # layer 0's neighbourhood term passes through a learned projection
+        raise NotImplementedError(
+            "--use-pp does not combine with --aggregator pool")
     feat = rp.ndata["feat"]
     size = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
@@ -170,10 +174,14 @@ def precompute(rp: RuntimePartition, args) -> torch.Tensor:
 
 
 def create_model(layer_size, args):
+    aggregator = getattr(args, "aggregator", "mean")
     if args.model == "graphsage":
         return GraphSAGE(layer_size, F.relu, args.use_pp, norm=args.norm,
                          dropout=args.dropout, n_linear=args.n_linear,
-                         train_size=args.n_train)
+                         train_size=args.n_train, aggregator=aggregator)
+    if aggregator != "mean":
+        raise NotImplementedError(
+            f"--aggregator {aggregator} supports graphsage only")
     if args.model == "gcn":
         from pipegcn_amd.models.gcn import GCN
 

@@ -27,7 +27,11 @@ heads under `--epoch`.
     python tools/microbench/gat_bench.py [--shape reddit] [--feats 256]
     python tools/microbench/gat_bench.py --epoch
     python tools/microbench/gat_bench.py [--epoch] --attn-drop 0.6
+`--pool` adds GraphSAGE with the max-pooling aggregator (csrc/hip/
+spmm_max.hip) to the `--epoch` models, built and timed the same way.
+
     python tools/microbench/gat_bench.py [--epoch] --v2
+    python tools/microbench/gat_bench.py --epoch --pool
 """
 import argparse
 import json
@@ -55,7 +59,12 @@ ap.add_argument("--attn-drop", "--attn_drop", type=float, default=0.0,
                 help="attention dropout of every GAT call (default: none)")
 ap.add_argument("--v2", action="store_true",
                 help="also time the GATv2 kernels / model")
+ap.add_argument("--pool", action="store_true",
+                help="with --epoch: also time GraphSAGE with the max-pooling "
+                     "aggregator")
 args = ap.parse_args()
+if args.pool and not args.epoch:
+    ap.error("--pool times whole epochs: use it with --epoch")
 if not 0.0 <= args.attn_drop < 1.0:
     ap.error("--attn-drop must be in [0, 1)")
 
@@ -128,6 +137,9 @@ def epoch_bench():
         if args.v2:
             models.append(("gatv2-4-heads", GATv2,
                            dict(n_heads=4, attn_drop=args.attn_drop), None))
+        if args.pool:
+            models.append(("graphsage-pool", GraphSAGE,
+                           dict(use_pp=False, aggregator="pool"), deg))
         for name, cls, kw, d in models:
             torch.manual_seed(0)
             model = cls(layer_size, Fn.relu, dropout=0.5, norm="layer",
