@@ -6,6 +6,13 @@ spellings and defaults. `--norm none` is normalized to None by check_args
 import argparse
 
 
+def _edge_drop_rate(text):
+    p = float(text)
+    if not 0.0 <= p < 1.0:
+        raise argparse.ArgumentTypeError(f"{text} is outside [0, 1)")
+    return p
+
+
 def create_parser(argv=None):
     parser = argparse.ArgumentParser(description="PipeGCN (MI355X-native)")
 
@@ -40,6 +47,14 @@ def create_parser(argv=None):
                              "probability in [0, 1) of dropping an edge's "
                              "attention coefficient, per head, in training "
                              "(--model gat, gatv2)")
+    parser.add_argument("--edge-drop", "--edge_drop", type=_edge_drop_rate,
+                        default=0.0,
+                        help="edge dropout (DropEdge) of the GraphSAGE-mean "
+                             "and GCN layers: probability in [0, 1) of "
+                             "removing an edge, redrawn per layer and step "
+                             "in training, the kept sum scaled by 1/(1-p) "
+                             "over the full-graph degrees (--model "
+                             "graphsage with --aggregator mean, gcn)")
     parser.add_argument("--aggregator", choices=["mean", "pool"],
                         default="mean",
                         help="neighbourhood aggregator of the GraphSAGE "

@@ -32,6 +32,23 @@ static torch::Tensor spmm(torch::Tensor indptr, torch::Tensor indices,
   return spmm_cpu(indptr, indices, feat, dst_scale, src_scale, num_rows);
 }
 
+// GPU-only: ops.spmm_drop composes the CPU path from torch ops
+static torch::Tensor spmm_drop(torch::Tensor indptr, torch::Tensor indices,
+                               torch::Tensor feat, torch::Tensor dst_scale,
+                               torch::Tensor src_scale,
+                               torch::Tensor row_order, int64_t num_rows,
+                               bool transposed, int64_t drop_key,
+                               int64_t drop_thr, double drop_scale,
+                               std::optional<torch::Tensor> n_live) {
+  TORCH_CHECK(feat.is_cuda() && feat.dim() == 2,
+              "spmm_drop is the GPU path");
+  auto out = torch::empty({num_rows, feat.size(1)}, feat.options());
+  spmm_drop_hip(indptr, indices, feat, dst_scale, src_scale, row_order, out,
+                n_live.value_or(torch::Tensor()), transposed, drop_key,
+                drop_thr, drop_scale);
+  return out;
+}
+
 // -> [out] or, with_arg, [out, arg]
 static std::vector<torch::Tensor> spmm_max(torch::Tensor indptr,
                                            torch::Tensor indices,
@@ -219,6 +236,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("indptr"), py::arg("indices"), py::arg("feat"),
         py::arg("dst_scale"), py::arg("src_scale"), py::arg("row_order"),
         py::arg("num_rows"), py::arg("n_live") = py::none());
+  m.def("spmm_drop", &spmm_drop,
+        "CSR SpMM over the edges the edge-dropout hash keeps, times "
+        "drop_scale",
+        py::arg("indptr"), py::arg("indices"), py::arg("feat"),
+        py::arg("dst_scale"), py::arg("src_scale"), py::arg("row_order"),
+        py::arg("num_rows"), py::arg("transposed"), py::arg("drop_key"),
+        py::arg("drop_thr"), py::arg("drop_scale"),
+        py::arg("n_live") = py::none());
   m.def("csr_simple", &csr_simple,
         "CSR without repeated entries in a row -> (indptr, indices, removed)");
   m.def("spmm_max", &spmm_max,

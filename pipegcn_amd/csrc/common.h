@@ -108,6 +108,19 @@ void spmm_csr_hip(torch::Tensor indptr, torch::Tensor indices,
 void scale_rows_live_hip(torch::Tensor g, torch::Tensor inv,
                          torch::Tensor scaled, torch::Tensor n_live);
 
+// Edge dropout (csrc/hip/spmm_drop.hip): spmm_csr_hip over the kept edges
+// only, times drop_scale = 1 / (1 - p). The edge of row r and gathered id c
+// is kept when the attention-dropout hash with one head (hip/attn_util.h) of
+// (u, v) = (c, r), or (r, c) if `transposed` (the CSC pass), is at least
+// drop_thr; drop_key and drop_thr are 32-bit values, drop_thr == 0 keeps
+// every edge. A dropped edge issues no gather. The other arguments and their
+// checks are spmm_csr_hip's; indices must be 16-byte aligned.
+void spmm_drop_hip(torch::Tensor indptr, torch::Tensor indices,
+                   torch::Tensor feat, torch::Tensor dst_scale,
+                   torch::Tensor src_scale, torch::Tensor row_order,
+                   torch::Tensor out, torch::Tensor n_live, bool transposed,
+                   int64_t drop_key, int64_t drop_thr, double drop_scale);
+
 // Packed rows (csrc/hip/spmm_packed.hip): one fixed-stride record per row of a
 // fp32 [N, F] tensor, in 4-byte words: mask_words header entries {uint32 mask,
 // uint32 exclusive prefix count} (one per 32 columns), padding up to hdr_words

@@ -26,10 +26,23 @@ from pipegcn_amd.models.sync_bn import SyncBatchNorm
 from pipegcn_amd.parallel import context as ctx
 
 
+def check_edge_drop(edge_drop):
+    if not 0.0 <= edge_drop < 1.0:
+        raise ValueError(f"edge_drop={edge_drop} is outside [0, 1)")
+    return edge_drop
+
+
 class GraphSAGELayer(nn.Module):
-    def __init__(self, in_feats, out_feats, bias=True, use_pp=False):
+    """`edge_drop` > 0 removes each edge with that probability in training,
+    redrawn at every call, and scales the kept sum by 1 / (1 - edge_drop)
+    (docs/DESIGN.md, "Edge dropout"); evaluation never drops. A use_pp
+    layer aggregates nothing in training, so it drops nothing."""
+
+    def __init__(self, in_feats, out_feats, bias=True, use_pp=False,
+                 edge_drop=0.0):
         super().__init__()
         self.use_pp = use_pp
+        self.edge_drop = check_edge_drop(edge_drop)
         if use_pp:
             self.linear = nn.Linear(2 * in_feats, out_feats, bias=bias)
         else:
@@ -56,7 +69,11 @@ class GraphSAGELayer(nn.Module):
                 return self.linear(feat)
             assert isinstance(graph, HaloGraph)
             inv_deg = (1.0 / in_deg.clamp(min=1.0)).contiguous()
-            ah = ops.spmm_mean(graph, feat, inv_deg)
+            if self.edge_drop > 0:
+                ah = ops.spmm_mean(graph, feat, inv_deg,
+                                   edge_drop=self.edge_drop)
+            else:
+                ah = ops.spmm_mean(graph, feat, inv_deg)
             x1 = feat[: graph.num_in]
             if feat.is_cuda:
                 # hand-written MFMA fused dual GEMM (one output pass)
@@ -200,7 +217,7 @@ AGGREGATORS = ("mean", "pool")
 class GraphSAGE(GNNBase):
     def __init__(self, layer_size, activation, use_pp, dropout=0.5,
                  norm="layer", train_size=None, n_linear=0,
-                 aggregator="mean"):
+                 aggregator="mean", edge_drop=0.0):
         if aggregator not in AGGREGATORS:
             raise ValueError(f"unknown aggregator {aggregator!r}: one of "
                              f"{', '.join(AGGREGATORS)}")
@@ -209,17 +226,25 @@ class GraphSAGE(GNNBase):
             # projection, so there is nothing to precompute
             raise NotImplementedError(
                 "--use-pp does not combine with --aggregator pool")
+        if check_edge_drop(edge_drop) > 0 and aggregator == "pool":
+            # a masked max gather does not exist (docs/ROADMAP.md)
+            raise NotImplementedError(
+                "--edge-drop does not combine with --aggregator pool")
         super().__init__(layer_size, activation, dropout, norm, train_size,
-                         n_linear, use_pp=use_pp, aggregator=aggregator)
+                         n_linear, use_pp=use_pp, aggregator=aggregator,
+                         edge_drop=edge_drop)
         self.use_pp = use_pp
         self.aggregator = aggregator
+        self.edge_drop = edge_drop
 
-    def make_conv(self, i, in_feats, out_feats, use_pp, aggregator):
+    def make_conv(self, i, in_feats, out_feats, use_pp, aggregator,
+                  edge_drop):
         if aggregator == "pool":
             return SAGEPoolLayer(in_feats, out_feats)
         # use_pp applies to the first layer only: its input already holds
         # [feat ‖ mean_agg], precomputed once
-        return GraphSAGELayer(in_feats, out_feats, use_pp=use_pp and i == 0)
+        return GraphSAGELayer(in_feats, out_feats, use_pp=use_pp and i == 0,
+                              edge_drop=edge_drop)
 
     def _exchanges_input(self, i):
         # a use_pp first layer aggregates nothing, so it fetches no halo rows

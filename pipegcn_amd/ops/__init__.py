@@ -283,14 +283,63 @@ class _SpmmMean(torch.autograd.Function):
         return None, grad_feat, None
 
 
-def spmm_mean(graph: HaloGraph, feat: torch.Tensor,
-              inv_deg: torch.Tensor) -> torch.Tensor:
+class _SpmmMeanDrop(torch.autograd.Function):
+    """_SpmmMean over the edges one edge-dropout draw keeps, times
+    1 / (1 - p): ah = D^{-1} (A o K) h / (1 - p), backward = its transpose
+    over the same kept set. Only drop = (key, thr, scale) travels from the
+    forward to the backward; both passes recompute the keep bits."""
+
+    @staticmethod
+    def forward(ctx, graph: HaloGraph, feat: torch.Tensor,
+                inv_deg: torch.Tensor, drop):
+        ctx.graph, ctx.drop = graph, drop
+        ctx.save_for_backward(inv_deg)
+        # the masked dense kernel: there is no masked packed gather
+        # (docs/ROADMAP.md)
+        return spmm_drop(graph.csr, feat, inv_deg, drop=drop)
+
+    @staticmethod
+    def backward(ctx, grad_out: torch.Tensor):
+        (inv_deg,) = ctx.saved_tensors
+        g, drop = ctx.graph, ctx.drop
+        # the two branches of _SpmmMean.backward, cost model and all
+        if g.csc.nnz > grad_out.numel():
+            n_live = None
+            if grad_out.is_cuda:
+                scaled, n_live = scale_rows_live(grad_out, inv_deg)
+                if os.environ.get("PIPEGCN_SPMM_LIVE", "1") == "0":
+                    n_live = None
+            else:
+                scaled = grad_out * inv_deg.unsqueeze(1).to(grad_out.dtype)
+            grad_feat = spmm_drop(g.csc, scaled, drop=drop, transposed=True,
+                                  n_live=n_live)
+        else:
+            grad_feat = spmm_drop(g.csc, grad_out.contiguous(),
+                                  src_scale=inv_deg, drop=drop,
+                                  transposed=True)
+        return None, grad_feat, None, None
+
+
+def spmm_mean(graph: HaloGraph, feat: torch.Tensor, inv_deg: torch.Tensor,
+              edge_drop: float = 0.0,
+              seed: Optional[int] = None) -> torch.Tensor:
     """Differentiable mean-aggregation over the halo graph.
 
     inv_deg is 1/in_degree of the dst nodes (full-graph degrees, precomputed
     before partitioning — reference semantics, /root/reference/helper/utils.py:142).
+
+    edge_drop in [0, 1) removes each edge with that probability for this
+    call (DropEdge) and scales the sum over the kept ones by
+    1 / (1 - edge_drop); inv_deg stays as given, there is no re-normalisation
+    over the kept edges. The mask is `edge_drop_keep(u, v, seed, edge_drop)`
+    on local ids, the same in the forward and the backward. seed defaults to
+    a draw from torch's host generator; edge_drop == 0 draws nothing and is
+    the path this function always took.
     """
-    return _SpmmMean.apply(graph, feat, inv_deg)
+    drop = edge_drop_args("spmm_mean", edge_drop, seed)
+    if drop[1] == 0:
+        return _SpmmMean.apply(graph, feat, inv_deg)
+    return _SpmmMeanDrop.apply(graph, feat, inv_deg, drop)
 
 
 def _spmm_max_check(csr: CSR, z: torch.Tensor) -> None:
@@ -467,6 +516,97 @@ def _edge_endpoints(csr: CSR):
     v = torch.repeat_interleave(
         torch.arange(csr.num_rows, device=csr.indices.device), deg)
     return csr.indices.long(), v
+
+
+def edge_drop_keep(u: torch.Tensor, v: torch.Tensor, seed: int,
+                   p: float) -> torch.Tensor:
+    """Edge-dropout keep bits of the edges u[i] -> v[i]: bool [n].
+
+    The attention-dropout hash with one head, `gat_dropout_keep(u, v, 1,
+    seed, p)[:, 0]`: the bit-identical torch mirror of what
+    csrc/hip/spmm_drop.hip evaluates per edge. A function of (seed, u, v)
+    on local node ids only, so the CSR and the CSC pass agree on it and
+    duplicate (u, v) edges share it."""
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"edge_drop_keep: p={p} is outside [0, 1)")
+    key, thr, _ = _gat_dropout_params(seed, p)
+    return _gat_keep_hash(u, v, 1, key)[:, 0] >= thr
+
+
+def edge_drop_args(op: str, p: float, seed: Optional[int] = None):
+    """drop = (key, thr, scale) of one edge-dropout draw for `op`'s
+    messages, derived as the attention dropout derives them
+    (`_gat_dropout_params`); (0, 0, 1.0) keeps every edge. When p is
+    positive and no seed is given, one is drawn from torch's host generator
+    (no device sync); p == 0 draws nothing."""
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"{op}: edge_drop={p} is outside [0, 1)")
+    if p == 0.0:
+        return 0, 0, 1.0
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    return _gat_dropout_params(seed, p)
+
+
+def spmm_drop(csr: CSR, feat: torch.Tensor,
+              scale: Optional[torch.Tensor] = None,
+              src_scale: Optional[torch.Tensor] = None, *,
+              p: Optional[float] = None, seed: Optional[int] = None,
+              transposed: bool = False,
+              n_live: Optional[torch.Tensor] = None,
+              drop=None) -> torch.Tensor:
+    """`spmm(csr, feat, scale, src_scale, n_live)` over the edges an
+    edge-dropout draw keeps, times 1 / (1 - p) (docs/DESIGN.md, "Edge
+    dropout"). Not differentiable by itself: `spmm_mean(edge_drop=...)` and
+    the GCN layer pair it with its transpose.
+
+    The edge of row r and column c is kept when `edge_drop_keep(c, r, seed,
+    p)` says so; with transposed=True (csr is a CSC: rows are sources) when
+    `edge_drop_keep(r, c, seed, p)` does, so a graph's CSR and CSC drop the
+    same edges for the same seed. p in [0, 1); seed defaults to one draw
+    from torch's host generator when p > 0. drop = (key, thr, scale), as
+    `edge_drop_args` returns it, stands in for (p, seed): a backward repeats
+    its forward's draw with it.
+
+    On the GPU a dropped edge issues no gather, and the result does not
+    depend on the row order. No row-order autotune of its own: the dense
+    path's cached decision for this (graph, F) if it made one, else the LPT
+    order. The CPU path composes the sum from torch ops in fp32."""
+    if drop is None:
+        if p is None:
+            raise ValueError("spmm_drop: give p (and seed) or drop")
+        drop = edge_drop_args("spmm_drop", p, seed)
+    key, thr, drop_scale = drop
+    if feat.dim() != 2 or feat.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("spmm_drop: feat must be a fp32 or bf16 [nodes, F] "
+                         f"tensor, got {tuple(feat.shape)} {feat.dtype}")
+    if feat.shape[0] < csr.num_cols:
+        raise ValueError(
+            f"spmm_drop: feat has {feat.shape[0]} rows but the graph "
+            f"references {csr.num_cols} source nodes (an under-sized feat "
+            "would be an out-of-bounds GPU gather)")
+    if feat.is_cuda:
+        # n_live together with src_scale is refused there, as in spmm
+        s = scale if scale is not None else torch.Tensor()
+        ss = src_scale if src_scale is not None else torch.Tensor()
+        ro = _row_order(csr)
+        if getattr(csr, "_lpt_choice", {}).get(feat.shape[1]) is False:
+            ro = torch.Tensor()
+        return native().spmm_drop(csr.indptr, csr.indices, feat.contiguous(),
+                                  s, ss, ro, csr.num_rows, transposed, key,
+                                  thr, drop_scale, n_live)
+    # CPU: n_live only saves the GPU kernel memory traffic
+    col, row = _edge_endpoints(csr)
+    u, v = (row, col) if transposed else (col, row)
+    keep = _gat_keep_hash(u, v, 1, key)[:, 0] >= thr
+    col, row = col[keep], row[keep]
+    x = feat.float().index_select(0, col)
+    if src_scale is not None:
+        x = x * src_scale.float().index_select(0, col).unsqueeze(1)
+    out = torch.zeros(csr.num_rows, feat.shape[1]).index_add(0, row, x)
+    if scale is not None:
+        out = out * scale.float().unsqueeze(1)
+    return (out * drop_scale).to(feat.dtype)
 
 
 def _edge_softmax_aggregate_torch(csr: CSR, u, v, score, values, drop=None):

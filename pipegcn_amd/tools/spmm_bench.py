@@ -21,7 +21,12 @@ mean SpMM on the same graph, fp32 and bf16: max forward with and without the
 arg-max output, max backward over the duplicate-free CSC, dense mean forward
 and its transpose alternate in the same rounds.
 
+With --edge-drop it compares the masked kernel of edge dropout
+(csrc/hip/spmm_drop.hip) with the plain dense kernel, forward and transpose,
+at each rate and with every edge kept, alternating in the same rounds.
+
 Usage (on a GPU box):
+    python -m pipegcn_amd.tools.spmm_bench --f 256 --edge-drop 0.2 0.5 0.8
     python -m pipegcn_amd.tools.spmm_bench [--f 602 256] [--rounds 5]
     python -m pipegcn_amd.tools.spmm_bench --f 256 --density 0.25 0.5 1.0
     python -m pipegcn_amd.tools.spmm_bench --f 256 --dead-frac 0 0.34 0.92
@@ -241,6 +246,91 @@ def max_table(hg, E, widths, rounds, iters):
             del z, g, arg
 
 
+def edge_drop_table(hg, inv, widths, rates, dtype, rounds, iters):
+    """The masked kernel (csrc/hip/spmm_drop.hip) against the plain dense
+    one on the same graph and input: forward over the CSR and transpose over
+    the CSC, for each rate p and for "keep-all" (the masked kernel with thr =
+    0: every edge kept, so the pure cost of the hash and the queue). All
+    variants of one width alternate in the same rounds after warm-up. fp32
+    also times the packed forward (pack pass + packed gather) on inputs with
+    one half and one quarter of non-zeros, the path --edge-drop gives up.
+    Prints best ms with the median in brackets."""
+    from pipegcn_amd import native, ops
+
+    n = hg.num_all
+    csr, csc = hg.csr, hg.csc
+    none = torch.Tensor()
+    fp32 = dtype == torch.float32
+
+    def masked(m, x, s, transposed, drop):
+        return native().spmm_drop(m.indptr, m.indices, x, s, none,
+                                  m.row_order, m.num_rows, transposed, *drop)
+
+    for F in widths:
+        gen = torch.Generator(device="cuda").manual_seed(F)
+        z = torch.randn(n, F, device="cuda", generator=gen).to(dtype)
+        g = torch.randn(hg.num_in, F, device="cuda", generator=gen).to(dtype)
+        fns = {
+            ("plain", "fwd"): lambda: native().spmm(
+                csr.indptr, csr.indices, z, inv, none, csr.row_order,
+                csr.num_rows),
+            ("plain", "T"): lambda: native().spmm(
+                csc.indptr, csc.indices, g, none, none, csc.row_order,
+                csc.num_rows),
+        }
+        drops = {"keep-all": (0, 0, 1.0)}
+        for p in rates:
+            drops[f"{p:g}"] = ops.edge_drop_args("spmm_bench", p, 1234)
+        for name, drop in drops.items():
+            fns[(name, "fwd")] = \
+                lambda drop=drop: masked(csr, z, inv, False, drop)
+            fns[(name, "T")] = \
+                lambda drop=drop: masked(csc, g, none, True, drop)
+        # keeping everything is the plain product up to summation order
+        ref = fns[("plain", "fwd")]().float()
+        err = (fns[("keep-all", "fwd")]().float() - ref).abs().max()
+        assert err <= 1e-2 * ref.abs().max(), f"F={F}: keep-all differs"
+        del ref
+        if fp32:
+            for d in (0.5, 0.25):
+                zd = z * (torch.rand(n, F, device="cuda", generator=gen) < d)
+                fns[(f"packed d={d:g}", "fwd")] = \
+                    lambda zd=zd: native().spmm_packed(
+                        csr.indptr, csr.indices, native().pack_rows(zd), F,
+                        inv, csr.row_order, csr.num_rows)
+        for fn in fns.values():
+            fn()
+            fn()
+        times = {k: [] for k in fns}
+        for _ in range(rounds):
+            for k, fn in fns.items():
+                torch.cuda.synchronize()
+                t0 = time.time()
+                for _ in range(iters):
+                    fn()
+                torch.cuda.synchronize()
+                times[k].append((time.time() - t0) / iters * 1e3)
+        best = {k: min(t) for k, t in times.items()}
+        med = {k: sorted(t)[len(t) // 2] for k, t in times.items()}
+        dname = "fp32" if fp32 else "bf16"
+        print(f"{dname} F={F}: best ms [median] over {rounds} rounds of "
+              f"{iters}")
+        print("  variant         |       forward      vs plain |"
+              "      transpose     vs plain")
+        for name in ["plain"] + list(drops):
+            f, t = (name, "fwd"), (name, "T")
+            print(f"  {name:15s} | {best[f]:8.2f} [{med[f]:7.2f}]"
+                  f"  {best[f] / best[('plain', 'fwd')]:6.3f}x |"
+                  f" {best[t]:8.2f} [{med[t]:7.2f}]"
+                  f"  {best[t] / best[('plain', 'T')]:6.3f}x", flush=True)
+        for k in fns:
+            if k[0].startswith("packed"):
+                print(f"  {k[0]:15s} | {best[k]:8.2f} [{med[k]:7.2f}]"
+                      f"  {best[k] / best[('plain', 'fwd')]:6.3f}x |"
+                      "  (pack pass + packed gather)", flush=True)
+        del z, g, fns
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--f", type=int, nargs="+", default=[602, 256])
@@ -266,6 +356,13 @@ def main():
                          "aggregation (forward with and without arg, "
                          "backward) against the mean SpMM and its transpose, "
                          "fp32 and bf16, at --f (default 64 256 602)")
+    ap.add_argument("--edge-drop", type=float, nargs="+", default=None,
+                    metavar="P",
+                    help="instead of the lane-width A/B: for each F and "
+                         "each edge-dropout rate P, and for a keep-all run "
+                         "of the masked kernel, time the masked forward and "
+                         "transpose against the plain dense kernel (--dtype "
+                         "as given; fp32 adds the packed forward)")
     args = ap.parse_args()
 
     from pipegcn_amd import ops
@@ -278,6 +375,11 @@ def main():
     if args.max:
         widths = args.f if args.f != ap.get_default("f") else [64, 256, 602]
         max_table(hg, E, widths, args.rounds, args.iters)
+        return
+    if args.edge_drop:
+        edge_drop_table(hg, inv, args.f, args.edge_drop,
+                        torch.bfloat16 if args.dtype == "bf16"
+                        else torch.float32, args.rounds, args.iters)
         return
     if args.density:
         if args.dtype != "fp32":

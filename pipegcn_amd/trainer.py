@@ -175,10 +175,19 @@ def precompute(rp: RuntimePartition, args) -> torch.Tensor:
 
 def create_model(layer_size, args):
     aggregator = getattr(args, "aggregator", "mean")
+    edge_drop = getattr(args, "edge_drop", 0.0)
+    if edge_drop > 0 and (aggregator == "pool"
+                          or args.model in ("gat", "gatv2")):
+        # a masked max gather is a later item; GAT has --attn-drop
+        what = ("--aggregator pool" if aggregator == "pool"
+                else f"--model {args.model}")
+        raise NotImplementedError(
+            f"--edge-drop does not combine with {what}")
     if args.model == "graphsage":
         return GraphSAGE(layer_size, F.relu, args.use_pp, norm=args.norm,
                          dropout=args.dropout, n_linear=args.n_linear,
-                         train_size=args.n_train, aggregator=aggregator)
+                         train_size=args.n_train, aggregator=aggregator,
+                         edge_drop=edge_drop)
     if aggregator != "mean":
         raise NotImplementedError(
             f"--aggregator {aggregator} supports graphsage only")
@@ -187,7 +196,7 @@ def create_model(layer_size, args):
 
         return GCN(layer_size, F.relu, args.use_pp, norm=args.norm,
                    dropout=args.dropout, n_linear=args.n_linear,
-                   train_size=args.n_train)
+                   train_size=args.n_train, edge_drop=edge_drop)
     if args.model == "gat":
         from pipegcn_amd.models.gat import GAT
 

@@ -24,6 +24,7 @@ ext = CUDAExtension(
         "pipegcn_amd/csrc/hip/kernels.hip",
         "pipegcn_amd/csrc/hip/spmm_packed.hip",
         "pipegcn_amd/csrc/hip/spmm_max.hip",
+        "pipegcn_amd/csrc/hip/spmm_drop.hip",
         "pipegcn_amd/csrc/hip/dual_gemm.hip",
         "pipegcn_amd/csrc/hip/elementwise.hip",
         "pipegcn_amd/csrc/hip/wgrad.hip",

@@ -32,6 +32,11 @@ spmm_max.hip) to the `--epoch` models, built and timed the same way.
 
     python tools/microbench/gat_bench.py [--epoch] --v2
     python tools/microbench/gat_bench.py --epoch --pool
+
+`--edge-drop P` adds GraphSAGE-mean and GCN with edge dropout P (csrc/hip/
+spmm_drop.hip) to the `--epoch` models, beside the same models without it.
+
+    python tools/microbench/gat_bench.py --epoch --edge-drop 0.5
 """
 import argparse
 import json
@@ -62,9 +67,16 @@ ap.add_argument("--v2", action="store_true",
 ap.add_argument("--pool", action="store_true",
                 help="with --epoch: also time GraphSAGE with the max-pooling "
                      "aggregator")
+ap.add_argument("--edge-drop", "--edge_drop", type=float, default=0.0,
+                help="with --epoch: also time GraphSAGE-mean and GCN with "
+                     "this edge dropout")
 args = ap.parse_args()
 if args.pool and not args.epoch:
     ap.error("--pool times whole epochs: use it with --epoch")
+if args.edge_drop and not args.epoch:
+    ap.error("--edge-drop times whole epochs: use it with --epoch")
+if not 0.0 <= args.edge_drop < 1.0:
+    ap.error("--edge-drop must be in [0, 1)")
 if not 0.0 <= args.attn_drop < 1.0:
     ap.error("--attn-drop must be in [0, 1)")
 
@@ -140,6 +152,11 @@ def epoch_bench():
         if args.pool:
             models.append(("graphsage-pool", GraphSAGE,
                            dict(use_pp=False, aggregator="pool"), deg))
+        if args.edge_drop > 0:
+            models.append(("graphsage-edge-drop", GraphSAGE,
+                           dict(use_pp=False, edge_drop=args.edge_drop), deg))
+            models.append(("gcn-edge-drop", GCN,
+                           dict(edge_drop=args.edge_drop), deg_all))
         for name, cls, kw, d in models:
             torch.manual_seed(0)
             model = cls(layer_size, Fn.relu, dropout=0.5, norm="layer",
@@ -160,6 +177,7 @@ def epoch_bench():
         print(json.dumps(dict(mode="epoch", shape=args.shape, dtype=dname,
                               hidden=256, layers=3,
                               attn_drop=args.attn_drop,
+                              edge_drop=args.edge_drop,
                               ms_per_epoch={k: round(v, 2)
                                             for k, v in ms.items()},
                               peak_gb=round(
