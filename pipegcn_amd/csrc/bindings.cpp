@@ -14,13 +14,21 @@ static torch::Tensor spmm(torch::Tensor indptr, torch::Tensor indices,
                           torch::Tensor feat, torch::Tensor dst_scale,
                           torch::Tensor src_scale, torch::Tensor row_order,
                           int64_t num_rows,
-                          std::optional<torch::Tensor> n_live) {
+                          std::optional<torch::Tensor> n_live,
+                          std::optional<torch::Tensor> add_rows,
+                          int64_t n_add,
+                          std::optional<torch::Tensor> drop_mask,
+                          double drop_scale) {
   if (feat.is_cuda()) {
     auto out = torch::empty({num_rows, feat.size(1)}, feat.options());
     spmm_csr_hip(indptr, indices, feat, dst_scale, src_scale, row_order,
-                 out, n_live.value_or(torch::Tensor()));
+                 out, n_live.value_or(torch::Tensor()),
+                 add_rows.value_or(torch::Tensor()), n_add,
+                 drop_mask.value_or(torch::Tensor()), drop_scale);
     return out;
   }
+  TORCH_CHECK(!add_rows.has_value() && !drop_mask.has_value(),
+              "spmm: the add/dropout epilogue is the GPU path");
   // n_live only saves the GPU kernel memory traffic: the CPU result is the
   // same with or without it
   if (feat.scalar_type() == torch::kBFloat16) {
@@ -231,11 +239,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("build_csr", &build_csr, "COO -> CSR (counting sort by dst)");
   m.def("partition_graph", &partition_graph_cpu,
         "BFS-grown + refined k-way partitioner (cut/vol objective)");
-  // n_live trails with a default: calls without it run what they ran before
+  // n_live and the add/dropout epilogue trail with defaults: calls without
+  // them run what they ran before
   m.def("spmm", &spmm, "CSR SpMM with fused scale epilogue (fwd & transpose)",
         py::arg("indptr"), py::arg("indices"), py::arg("feat"),
         py::arg("dst_scale"), py::arg("src_scale"), py::arg("row_order"),
-        py::arg("num_rows"), py::arg("n_live") = py::none());
+        py::arg("num_rows"), py::arg("n_live") = py::none(),
+        py::arg("add_rows") = py::none(), py::arg("n_add") = 0,
+        py::arg("drop_mask") = py::none(), py::arg("drop_scale") = 1.0);
   m.def("spmm_drop", &spmm_drop,
         "CSR SpMM over the edges the edge-dropout hash keeps, times "
         "drop_scale",

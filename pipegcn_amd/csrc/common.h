@@ -95,10 +95,18 @@ torch::Tensor spmm_max_bwd_hip(torch::Tensor indptr, torch::Tensor indices,
 // in device memory, read by the kernel. The caller guarantees that the rows of
 // feat from *n_live on are all zero; their gathers are then redirected to row
 // *n_live. The result is bitwise the one without it.
+// Epilogue (optional, not with dst_scale): add_rows [>= n_add, F] in feat's
+// dtype, unit column stride and any row stride, is added to output rows
+// r < n_add; drop_mask, the uint8 bit mask dropout_fwd_hip writes over a
+// [num_rows, F] tensor, then zeroes the elements whose bit is clear and
+// multiplies the others by drop_scale. Bitwise dropout_bwd_hip of the eager
+// sum of the plain result and the zero-padded add_rows.
 void spmm_csr_hip(torch::Tensor indptr, torch::Tensor indices,
                   torch::Tensor feat, torch::Tensor dst_scale,
                   torch::Tensor src_scale, torch::Tensor row_order,
-                  torch::Tensor out, torch::Tensor n_live = {});
+                  torch::Tensor out, torch::Tensor n_live = {},
+                  torch::Tensor add_rows = {}, int64_t n_add = 0,
+                  torch::Tensor drop_mask = {}, double drop_scale = 1.0);
 
 // scaled[r,:] = g[r,:] * inv[r] (for bf16, inv rounded to bf16 first, as the
 // eager product rounds it), and in the same pass *n_live = 1 + the largest r

@@ -46,10 +46,56 @@ __device__ __forceinline__ void st(__hip_bfloat16* p, float v) {
   *p = __float2bfloat16(v);
 }
 
+// a fp32 value as a store to T and a load back would leave it
+__device__ __forceinline__ float rounded(float v, const float*) { return v; }
+__device__ __forceinline__ float rounded(float v, const __hip_bfloat16*) {
+  return __bfloat162float(__float2bfloat16(v));
+}
+
 // ---------------------------------------------------------------------------
 // CSR SpMM: out[r, fchunk] = scale[r] * sum_e feat[indices[e], fchunk]
 // One wave per (row, chunk) pair, grid-stride. VEC in {8, 4, 2, 1}.
 // ---------------------------------------------------------------------------
+
+// What the EPI instances do to a finished sum before they store it (the
+// fused layer backward; docs/DESIGN.md, "Fused layer backward"):
+//   v = acc + (r < n_add ? add_rows[r, c] : 0)     when add_rows is set
+//   v = bit(r * F + c) of drop_mask ? v * drop_scale : 0   when drop_mask is
+// add_rows has add_stride elements between rows (a column slice of a wider
+// tensor); drop_mask is the bit mask dropout_fwd_kernel wrote over the
+// flattened [num_rows, F] tensor, so at an F that is no multiple of 8 a byte
+// straddles two rows. Every step rounds to T as the three kernels it
+// replaces did (this kernel's store, the accumulate, dropout_bwd_kernel), so
+// the result is theirs bit for bit.
+struct SpmmEpilogue {
+  const void* add_rows;
+  int64_t add_stride;
+  int64_t n_add;
+  const uint8_t* drop_mask;
+  float drop_scale;
+};
+
+template <typename T>
+__device__ __forceinline__ float spmm_epilogue(const SpmmEpilogue& ep,
+                                               float acc, int64_t r,
+                                               int64_t c, int64_t F) {
+  const T* tag = nullptr;
+  float v = rounded(acc, tag);
+  if (ep.add_rows != nullptr) {
+    // rows past n_add add the +0.0 the padded accumulate added: a sum that
+    // rounded to -0.0 comes out +0.0 there too
+    const float a = r < ep.n_add ? to_f32(static_cast<const T*>(
+                                       ep.add_rows)[r * ep.add_stride + c])
+                                 : 0.f;
+    v = rounded(v + a, tag);
+  }
+  if (ep.drop_mask != nullptr) {
+    const int64_t i = r * F + c;
+    const bool keep = (ep.drop_mask[i >> 3] >> (i & 7)) & 1;
+    v = keep ? rounded(v * ep.drop_scale, tag) : 0.f;
+  }
+  return v;
+}
 
 // Chunk-inner order (consecutive waves take the chunks of one row): sweeping
 // one column panel at a time to keep it cache-resident measured slower at
@@ -66,7 +112,10 @@ __device__ __forceinline__ void st(__hip_bfloat16* p, float v) {
 // the loads of dead rows all hit the one zero row n_live, which stays in
 // L1/L2, and never reach HBM. Same loads, same order, same adds: the result
 // is bitwise that of the plain kernel.
-template <typename T, int VEC, bool HAS_SRC_SCALE, bool HAS_LIVE>
+//
+// EPI: the add / dropout epilogue above, instead of dst_scale. A template
+// flag, so the instances launched without an epilogue are the code they were.
+template <typename T, int VEC, bool HAS_SRC_SCALE, bool HAS_LIVE, bool EPI>
 __global__ void spmm_csr_kernel(const int64_t* __restrict__ indptr,
                                 const int32_t* __restrict__ indices,
                                 const T* __restrict__ feat,
@@ -75,7 +124,8 @@ __global__ void spmm_csr_kernel(const int64_t* __restrict__ indptr,
                                 const int32_t* __restrict__ row_order,
                                 T* __restrict__ out, int64_t num_rows,
                                 int64_t F, int64_t nchunks,
-                                const int32_t* __restrict__ n_live) {
+                                const int32_t* __restrict__ n_live,
+                                SpmmEpilogue ep) {
   static_assert(!(HAS_SRC_SCALE && HAS_LIVE),
                 "the redirect would also redirect the scale's index");
   // read once per wave (a scalar load); max() only keeps a corrupt count
@@ -166,9 +216,16 @@ __global__ void spmm_csr_kernel(const int64_t* __restrict__ indptr,
         for (int k = 0; k < VEC; ++k)
           acc[k] += s * to_f32(feat[u * F + f0 + k]);
       }
-      const float s = dst_scale ? dst_scale[r] : 1.f;
+      if constexpr (EPI) {
 #pragma unroll
-      for (int k = 0; k < VEC; ++k) st_nt(out + r * F + f0 + k, acc[k] * s);
+        for (int k = 0; k < VEC; ++k)
+          st_nt(out + r * F + f0 + k,
+                spmm_epilogue<T>(ep, acc[k], r, f0 + k, F));
+      } else {
+        const float s = dst_scale ? dst_scale[r] : 1.f;
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) st_nt(out + r * F + f0 + k, acc[k] * s);
+      }
     } else {
       // ragged tail chunk: scalar guarded
       for (; e < e_end; ++e) {
@@ -177,9 +234,15 @@ __global__ void spmm_csr_kernel(const int64_t* __restrict__ indptr,
         for (int k = 0; k < VEC && f0 + k < F; ++k)
           acc[k] += s * to_f32(feat[u * F + f0 + k]);
       }
-      const float s = dst_scale ? dst_scale[r] : 1.f;
-      for (int k = 0; k < VEC && f0 + k < F; ++k)
-        st(out + r * F + f0 + k, acc[k] * s);
+      if constexpr (EPI) {
+        for (int k = 0; k < VEC && f0 + k < F; ++k)
+          st(out + r * F + f0 + k,
+             spmm_epilogue<T>(ep, acc[k], r, f0 + k, F));
+      } else {
+        const float s = dst_scale ? dst_scale[r] : 1.f;
+        for (int k = 0; k < VEC && f0 + k < F; ++k)
+          st(out + r * F + f0 + k, acc[k] * s);
+      }
     }
   }
 }
@@ -188,8 +251,8 @@ template <typename T, int VEC>
 void launch_spmm(const int64_t* indptr, const int32_t* indices,
                  const T* feat, const float* dst_scale,
                  const float* src_scale, const int32_t* row_order,
-                 const int32_t* n_live, T* out, int64_t num_rows, int64_t F,
-                 hipStream_t stream) {
+                 const int32_t* n_live, const SpmmEpilogue* epi, T* out,
+                 int64_t num_rows, int64_t F, hipStream_t stream) {
   const int64_t nchunks = (F + kWave * VEC - 1) / (kWave * VEC);
   constexpr int threads = 256;  // 4 whole waves: the kernel keeps the
   static_assert(threads % kWave == 0);  // wave index in a scalar register
@@ -197,14 +260,24 @@ void launch_spmm(const int64_t* indptr, const int32_t* indices,
   auto launch = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), 0, stream, indptr,
                        indices, feat, dst_scale, src_scale, row_order, out,
-                       num_rows, F, nchunks, n_live);
+                       num_rows, F, nchunks, n_live,
+                       epi ? *epi : SpmmEpilogue{});
   };
-  if (n_live)  // spmm_csr_hip refuses it together with src_scale
-    launch(HIP_KERNEL_NAME(spmm_csr_kernel<T, VEC, false, true>));
-  else if (src_scale)
-    launch(HIP_KERNEL_NAME(spmm_csr_kernel<T, VEC, true, false>));
-  else
-    launch(HIP_KERNEL_NAME(spmm_csr_kernel<T, VEC, false, false>));
+  // spmm_csr_hip refuses n_live with src_scale, and an epilogue with dst_scale
+  if (epi) {
+    if (n_live)
+      launch(HIP_KERNEL_NAME(spmm_csr_kernel<T, VEC, false, true, true>));
+    else if (src_scale)
+      launch(HIP_KERNEL_NAME(spmm_csr_kernel<T, VEC, true, false, true>));
+    else
+      launch(HIP_KERNEL_NAME(spmm_csr_kernel<T, VEC, false, false, true>));
+  } else if (n_live) {
+    launch(HIP_KERNEL_NAME(spmm_csr_kernel<T, VEC, false, true, false>));
+  } else if (src_scale) {
+    launch(HIP_KERNEL_NAME(spmm_csr_kernel<T, VEC, true, false, false>));
+  } else {
+    launch(HIP_KERNEL_NAME(spmm_csr_kernel<T, VEC, false, false, false>));
+  }
   check_launch();
 }
 
@@ -288,6 +361,11 @@ __global__ void ema_kernel(float* __restrict__ avg,
 // row stripes into partials [nblk, F]; a tiny second pass (torch) reduces.
 // ---------------------------------------------------------------------------
 
+// rows whose loads a thread issues before it adds them: the adds stay in row
+// order, so the sum is the one a row at a time gives, bit for bit, and the
+// loads no longer wait for one another
+constexpr int kColsumRows = 16;
+
 template <int VEC>
 __global__ void colsum_partial_kernel(const float* __restrict__ x,
                                       float* __restrict__ partials,
@@ -303,7 +381,19 @@ __global__ void colsum_partial_kernel(const float* __restrict__ x,
 #pragma unroll
     for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
     if (f0 + VEC <= F) {
-      for (int64_t r = r0; r < r1; ++r) {
+      int64_t r = r0;
+      for (; r + kColsumRows <= r1; r += kColsumRows) {
+        float v[kColsumRows][VEC];
+#pragma unroll
+        for (int j = 0; j < kColsumRows; ++j)
+#pragma unroll
+          for (int k = 0; k < VEC; ++k) v[j][k] = x[(r + j) * F + f0 + k];
+#pragma unroll
+        for (int j = 0; j < kColsumRows; ++j)
+#pragma unroll
+          for (int k = 0; k < VEC; ++k) acc[k] += v[j][k];
+      }
+      for (; r < r1; ++r) {
 #pragma unroll
         for (int k = 0; k < VEC; ++k) acc[k] += x[r * F + f0 + k];
       }
@@ -349,22 +439,25 @@ int pick_vec(int64_t F, int64_t num_rows, int64_t elem_size) {
 template <typename T>
 void spmm_dispatch(torch::Tensor& indptr, torch::Tensor& indices,
                    torch::Tensor& feat, const float* dsp, const float* ssp,
-                   const int32_t* rop, const int32_t* nlp, torch::Tensor& out,
+                   const int32_t* rop, const int32_t* nlp,
+                   const SpmmEpilogue* epi, torch::Tensor& out,
                    int64_t num_rows, int64_t F, int vec, hipStream_t stream) {
   const T* fp = reinterpret_cast<const T*>(feat.data_ptr());
   T* op = reinterpret_cast<T*>(out.data_ptr());
   const int64_t* ip = indptr.data_ptr<int64_t>();
   const int32_t* xp = indices.data_ptr<int32_t>();
   dispatch_vec(vec, [&](auto v) {
-    launch_spmm<T, v.value>(ip, xp, fp, dsp, ssp, rop, nlp, op, num_rows, F,
-                            stream);
+    launch_spmm<T, v.value>(ip, xp, fp, dsp, ssp, rop, nlp, epi, op, num_rows,
+                            F, stream);
   });
 }
 
 void spmm_csr_hip(torch::Tensor indptr, torch::Tensor indices,
                   torch::Tensor feat, torch::Tensor dst_scale,
                   torch::Tensor src_scale, torch::Tensor row_order,
-                  torch::Tensor out, torch::Tensor n_live) {
+                  torch::Tensor out, torch::Tensor n_live,
+                  torch::Tensor add_rows, int64_t n_add,
+                  torch::Tensor drop_mask, double drop_scale) {
   TORCH_CHECK(feat.is_cuda() && out.is_cuda(), "spmm_csr_hip: device tensors");
   const bool bf16 = feat.scalar_type() == torch::kBFloat16;
   TORCH_CHECK(bf16 || feat.scalar_type() == torch::kFloat,
@@ -405,13 +498,42 @@ void spmm_csr_hip(torch::Tensor indptr, torch::Tensor indices,
                 "would pick another row's scale)");
     nlp = n_live.data_ptr<int32_t>();
   }
+  SpmmEpilogue ep{};
+  if (add_rows.defined() && add_rows.numel() > 0) {
+    TORCH_CHECK(add_rows.is_cuda() && add_rows.dim() == 2 &&
+                    add_rows.scalar_type() == feat.scalar_type() &&
+                    add_rows.size(1) == F &&
+                    (F == 1 || add_rows.stride(1) == 1),
+                "spmm: add_rows is [n_add, F] in feat's dtype, rows "
+                "contiguous");
+    TORCH_CHECK(n_add >= 0 && n_add <= add_rows.size(0),
+                "spmm: n_add exceeds add_rows");
+    TORCH_CHECK(add_rows.size(0) <= 1 || add_rows.stride(0) >= F,
+                "spmm: add_rows rows overlap");
+    ep.add_rows = add_rows.data_ptr();
+    ep.add_stride = add_rows.stride(0);
+    ep.n_add = n_add;
+  }
+  if (drop_mask.defined() && drop_mask.numel() > 0) {
+    TORCH_CHECK(drop_mask.is_cuda() && drop_mask.is_contiguous() &&
+                    drop_mask.scalar_type() == torch::kUInt8 &&
+                    drop_mask.numel() >= (num_rows * F + 7) / 8,
+                "spmm: drop_mask holds one bit per output element (uint8)");
+    ep.drop_mask = drop_mask.data_ptr<uint8_t>();
+    ep.drop_scale = static_cast<float>(drop_scale);
+  }
+  const bool has_epi = ep.add_rows != nullptr || ep.drop_mask != nullptr;
+  TORCH_CHECK(!(has_epi && dsp != nullptr),
+              "spmm: the add/dropout epilogue and dst_scale do not combine "
+              "(acc * scale + add would round once)");
+  const SpmmEpilogue* epi = has_epi ? &ep : nullptr;
   auto stream = current_stream();
   const int vec = pick_vec(F, num_rows, bf16 ? 2 : 4);
   if (bf16)
     spmm_dispatch<__hip_bfloat16>(indptr, indices, feat, dsp, ssp, rop, nlp,
-                                  out, num_rows, F, vec, stream);
+                                  epi, out, num_rows, F, vec, stream);
   else
-    spmm_dispatch<float>(indptr, indices, feat, dsp, ssp, rop, nlp, out,
+    spmm_dispatch<float>(indptr, indices, feat, dsp, ssp, rop, nlp, epi, out,
                          num_rows, F, vec, stream);
 }
 

@@ -16,6 +16,7 @@ HaloGraph/FullGraph CSR structures and hand-written gfx950 SpMM:
 from __future__ import annotations
 
 import math
+import os
 
 import torch
 from torch import nn
@@ -63,12 +64,36 @@ class GraphSAGELayer(nn.Module):
             init(self.linear1)
             init(self.linear2)
 
-    def forward(self, graph, feat, in_deg=None):
+    def _can_fuse(self, feat):
+        return (self.training and not self.use_pp and self.edge_drop == 0
+                and feat.is_cuda)
+
+    def fuses_dropout(self, feat):
+        """Whether the model should hand this layer the tensor BEFORE feature
+        dropout together with the rate (`forward(..., dropout=p)`), so that
+        the training forward runs as the one fused node
+        (`ops.sage_mean_layer`). PIPEGCN_SAGE_FUSED=0 keeps the three
+        separate ops everywhere. The caller asks once per layer call."""
+        return (self._can_fuse(feat)
+                and os.environ.get("PIPEGCN_SAGE_FUSED", "1") != "0")
+
+    def forward(self, graph, feat, in_deg=None, dropout=None):
+        """dropout=None: feat is the layer's input as it is (the three
+        separate ops in training). dropout=p, p >= 0: feat is the tensor
+        before feature dropout and the fused node applies the rate p."""
+        if dropout is not None and not self._can_fuse(feat):
+            raise ValueError("GraphSAGELayer: only the fused training path "
+                             "(GPU, mean aggregation, no edge dropout, not "
+                             "use_pp) applies feature dropout itself")
         if self.training:
             if self.use_pp:
                 return self.linear(feat)
             assert isinstance(graph, HaloGraph)
             inv_deg = (1.0 / in_deg.clamp(min=1.0)).contiguous()
+            if dropout is not None:
+                return ops.sage_mean_layer(graph, feat, inv_deg,
+                                           self.linear1, self.linear2,
+                                           p=dropout)
             if self.edge_drop > 0:
                 ah = ops.spmm_mean(graph, feat, inv_deg,
                                    edge_drop=self.edge_drop)
@@ -184,8 +209,14 @@ class GNNBase(nn.Module):
             if i < self.n_layers - self.n_linear:
                 if self.training and self._exchanges_input(i):
                     h = ctx.buffer.update(i, h)
-                h = self._drop(h)
-                h = self.layers[i](g, h, in_deg)
+                layer = self.layers[i]
+                if (isinstance(layer, GraphSAGELayer)
+                        and layer.fuses_dropout(h)):
+                    # the layer's one node drops h itself
+                    h = layer(g, h, in_deg, dropout=self.dropout.p)
+                else:
+                    h = self._drop(h)
+                    h = layer(g, h, in_deg)
             else:
                 h = self._drop(h)
                 h = ops.linear(h, self.layers[i])

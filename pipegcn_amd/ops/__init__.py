@@ -54,17 +54,36 @@ def _tune_row_order(csr: CSR, feat, s, ss) -> bool:
     return times["lpt"] <= times["nat"]
 
 
+def dropout_scale(p: float) -> float:
+    """The fp32 factor 1 / (1 - p) as the dropout kernels form it: p is
+    quantised to 1/65536 first (csrc/hip/elementwise.hip)."""
+    p16 = int(p * 65536.0 + 0.5)
+    return (torch.tensor(1.0) / torch.tensor(1.0 - p16 / 65536.0)).item()
+
+
 def spmm(csr: CSR, feat: torch.Tensor,
          scale: Optional[torch.Tensor] = None,
          src_scale: Optional[torch.Tensor] = None,
-         n_live: Optional[torch.Tensor] = None) -> torch.Tensor:
+         n_live: Optional[torch.Tensor] = None, *,
+         add_rows: Optional[torch.Tensor] = None,
+         n_add: Optional[int] = None,
+         drop_mask: Optional[torch.Tensor] = None,
+         drop_scale: float = 1.0) -> torch.Tensor:
     """out[r,:] = scale[r] * sum_{u in N(r)} src_scale[u] * feat[u,:].
 
     n_live (GPU, not with src_scale): one int32 in device memory, the
     caller's promise that the rows of feat from n_live on are all zero (as
     `scale_rows_live` counts them). The kernel then gathers the one zero row
     n_live in their place, which stays in cache; the result is bitwise the
-    same (docs/DESIGN.md, "Dead gradient rows")."""
+    same (docs/DESIGN.md, "Dead gradient rows").
+
+    Epilogue (GPU, not with scale; docs/DESIGN.md, "Fused layer backward"):
+    add_rows [>= n_add, F] in feat's dtype (rows may be strided: a column
+    slice of a wider tensor) is added to the first n_add output rows
+    (default: all of add_rows); drop_mask is the uint8 bit mask
+    `dropout_fwd` wrote over a [num_rows, F] tensor, and an element whose
+    bit is clear becomes 0, the others are multiplied by drop_scale. The
+    result is bitwise `dropout_bwd(out + pad(add_rows), drop_mask)`."""
     if feat.shape[0] < csr.num_cols:
         raise ValueError(
             f"spmm: feat has {feat.shape[0]} rows but the graph references "
@@ -98,6 +117,18 @@ def spmm(csr: CSR, feat: torch.Tensor,
             cache[feat.shape[1]] = use_lpt
         if not use_lpt:
             ro = torch.Tensor()
+    if add_rows is not None or drop_mask is not None:
+        if scale is not None:
+            raise ValueError(
+                "spmm: the add/dropout epilogue does not combine with scale "
+                "(acc * scale + add would contract to one rounding)")
+        if not feat.is_cuda:
+            raise ValueError("spmm: the add/dropout epilogue is the GPU path")
+        if add_rows is not None and n_add is None:
+            n_add = add_rows.shape[0]
+        return native().spmm(csr.indptr, csr.indices, feat, s, ss, ro,
+                             csr.num_rows, n_live, add_rows, n_add or 0,
+                             drop_mask, drop_scale)
     if n_live is None:
         return native().spmm(csr.indptr, csr.indices, feat, s, ss,
                              ro, csr.num_rows)
@@ -236,6 +267,45 @@ def spmm_packed(csr: CSR, feat: torch.Tensor,
                                 feat.shape[1], s, ro, csr.num_rows)
 
 
+def _spmm_mean_forward(graph: HaloGraph, feat: torch.Tensor,
+                       inv_deg: torch.Tensor) -> torch.Tensor:
+    # the forward input is dropout's output (half zeros, three quarters
+    # after a ReLU): gather it packed. The backward's input is a gradient,
+    # dense in the rows that have one, and stays on the dense kernel.
+    if _spmm_packed_route(feat):
+        return spmm_packed(graph.csr, feat, inv_deg)
+    return spmm(graph.csr, feat, inv_deg)
+
+
+def _spmm_mean_backward(g: HaloGraph, grad_out: torch.Tensor,
+                        inv_deg: torch.Tensor, **epilogue) -> torch.Tensor:
+    """A^T D^{-1} grad_out; `epilogue` are spmm's add/dropout arguments (the
+    fused layer node), none for the plain op."""
+    # D^{-1} either as ONE streaming row-multiply on g or as the
+    # fused per-EDGE src_scale gather: the multiply costs ~3 passes
+    # over [rows,F], the gather ~one 4B load per edge plus its
+    # latency slot — dense graphs (reddit: nnz 115M > numel 60M,
+    # measured +1 ms/call for pre-scale) want the multiply, sparse
+    # wide ones (yelp: nnz 14M << numel 367M) want the gather
+    if g.csc.nnz > grad_out.numel():
+        if grad_out.is_cuda:
+            # the multiply also finds where the gradient's all-zero
+            # tail starts: the loss covers the train nodes, which are
+            # numbered first, so under the last layer every later row
+            # is zero, and the gather keeps those out of HBM. Other
+            # layers find n_live == rows and nothing changes.
+            # PIPEGCN_SPMM_LIVE=0 withholds the count.
+            scaled, n_live = scale_rows_live(grad_out, inv_deg)
+            if os.environ.get("PIPEGCN_SPMM_LIVE", "1") == "0":
+                n_live = None
+            return spmm(g.csc, scaled, None, n_live=n_live, **epilogue)
+        return spmm(g.csc,
+                    grad_out * inv_deg.unsqueeze(1).to(grad_out.dtype), None,
+                    **epilogue)
+    return spmm(g.csc, grad_out.contiguous(), None, src_scale=inv_deg,
+                **epilogue)
+
+
 class _SpmmMean(torch.autograd.Function):
     """ah = D^{-1} A h over the halo graph; backward = A^T D^{-1} g."""
 
@@ -244,43 +314,12 @@ class _SpmmMean(torch.autograd.Function):
                 inv_deg: torch.Tensor):
         ctx.graph = graph
         ctx.save_for_backward(inv_deg)
-        # the forward input is dropout's output (half zeros, three quarters
-        # after a ReLU): gather it packed. The backward's input is a gradient,
-        # dense in the rows that have one, and stays on the dense kernel.
-        if _spmm_packed_route(feat):
-            return spmm_packed(graph.csr, feat, inv_deg)
-        return spmm(graph.csr, feat, inv_deg)
+        return _spmm_mean_forward(graph, feat, inv_deg)
 
     @staticmethod
     def backward(ctx, grad_out: torch.Tensor):
         (inv_deg,) = ctx.saved_tensors
-        g = ctx.graph
-        # D^{-1} either as ONE streaming row-multiply on g or as the
-        # fused per-EDGE src_scale gather: the multiply costs ~3 passes
-        # over [rows,F], the gather ~one 4B load per edge plus its
-        # latency slot — dense graphs (reddit: nnz 115M > numel 60M,
-        # measured +1 ms/call for pre-scale) want the multiply, sparse
-        # wide ones (yelp: nnz 14M << numel 367M) want the gather
-        if g.csc.nnz > grad_out.numel():
-            if grad_out.is_cuda:
-                # the multiply also finds where the gradient's all-zero
-                # tail starts: the loss covers the train nodes, which are
-                # numbered first, so under the last layer every later row
-                # is zero, and the gather keeps those out of HBM. Other
-                # layers find n_live == rows and nothing changes.
-                # PIPEGCN_SPMM_LIVE=0 withholds the count.
-                scaled, n_live = scale_rows_live(grad_out, inv_deg)
-                if os.environ.get("PIPEGCN_SPMM_LIVE", "1") == "0":
-                    n_live = None
-                grad_feat = spmm(g.csc, scaled, None, n_live=n_live)
-            else:
-                grad_feat = spmm(
-                    g.csc,
-                    grad_out * inv_deg.unsqueeze(1).to(grad_out.dtype), None)
-        else:
-            grad_feat = spmm(g.csc, grad_out.contiguous(), None,
-                             src_scale=inv_deg)
-        return None, grad_feat, None
+        return None, _spmm_mean_backward(ctx.graph, grad_out, inv_deg), None
 
 
 class _SpmmMeanDrop(torch.autograd.Function):
@@ -953,58 +992,161 @@ class _SageDualLinear(torch.autograd.Function):
     def forward(ctx, x1, x2, w1, w2, b1, b2):
         ctx.save_for_backward(x1, x2, w1, w2)
         ctx.has_bias = b1 is not None
-        if (w1.size(0) < 64 or not x1.is_cuda
-                or x1.dtype != torch.float32):
-            # thin-N / CPU: the 128x128 MFMA tile would waste most of the
-            # block; rocBLAS pair instead (the op is memory-bound there)
-            out = torch.mm(x1, w1.t())
-            out.addmm_(x2, w2.t())
-            if b1 is not None:
-                out.add_(b1 + b2)
-            return out
-        bias = (b1 + b2) if b1 is not None else torch.Tensor()
-        return native().sage_dual_gemm(x1.contiguous(), x2.contiguous(),
-                                       w1.contiguous(), w2.contiguous(),
-                                       bias)
+        return _sage_dual_forward(x1, x2, w1, w2, b1, b2)
 
     @staticmethod
     def backward(ctx, g):
         x1, x2, w1, w2 = ctx.saved_tensors
         g = g.contiguous()
-        if g.is_cuda and g.dtype == torch.float32:
-            # NOTE: running the wgrad pair on a side stream under the
-            # dgrad was tried and measured WORSE (113.7 -> 114.7 ms
-            # epoch): the timeline is gap-free compute, so concurrent
-            # saturating kernels just share CUs plus event overhead.
-            # wgrad pair fused in one MFMA split-M kernel (g streamed
-            # once for both products; deterministic workspace reduce)
-            gw1, gw2 = native().dual_wgrad(g, x1.contiguous(),
-                                           x2.contiguous())
-            if g.size(1) >= 64 and w1.size(1) <= 256:
-                # dgrad pair fused in one MFMA kernel (g tile staged once
-                # for both weight contractions; measured par with rocBLAS
-                # at K=256 — 117 TF both; rocBLAS wins at K=512 (142 vs
-                # 123 TF) and K=602 (112 vs 95), hence the cap)
-                gx1, gx2 = native().dual_dgrad(g, w1.contiguous(),
-                                               w2.contiguous())
-            else:
-                # thin-N (the 41-class output layer) and wide-K (602:
-                # rocBLAS 112 vs our 95 TF — the unaligned 602-float rows
-                # and boundary k-tile cost us there): ONE GEMM against
-                # [w1 ‖ w2] so g is still read once
-                gx = g @ torch.cat((w1, w2), dim=1)
-                K = w1.size(1)
-                gx1, gx2 = gx[:, :K], gx[:, K:]
-        else:
-            gx1 = g @ w1
-            gx2 = g @ w2
-            gw1 = g.t() @ x1
-            gw2 = g.t() @ x2
-        if not ctx.has_bias:
-            return gx1, gx2, gw1, gw2, None, None
-        gb = native().colsum(g)  # two-phase column sum (fastest measured)
-        gb = gb.to(w1.dtype)
+        gw1, gw2, gb = _sage_param_grads(g, x1, x2, w1, ctx.has_bias)
+        gx1 = gx2 = None
+        # an input without a gradient (layer 0: both descend from the
+        # constant features) costs no dgrad
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            gx1, gx2 = _sage_dgrad(g, w1, w2, ctx.needs_input_grad[0],
+                                   ctx.needs_input_grad[1])
         return gx1, gx2, gw1, gw2, gb, gb
+
+
+def _sage_dual_forward(x1, x2, w1, w2, b1, b2):
+    if (w1.size(0) < 64 or not x1.is_cuda
+            or x1.dtype != torch.float32):
+        # thin-N / CPU: the 128x128 MFMA tile would waste most of the
+        # block; rocBLAS pair instead (the op is memory-bound there)
+        out = torch.mm(x1, w1.t())
+        out.addmm_(x2, w2.t())
+        if b1 is not None:
+            out.add_(b1 + b2)
+        return out
+    bias = (b1 + b2) if b1 is not None else torch.Tensor()
+    return native().sage_dual_gemm(x1.contiguous(), x2.contiguous(),
+                                   w1.contiguous(), w2.contiguous(),
+                                   bias)
+
+
+def _sage_param_grads(g, x1, x2, w1, has_bias):
+    """(gw1, gw2, gb) of the dual linear for a contiguous g; gb is None
+    without a bias."""
+    if g.is_cuda and g.dtype == torch.float32:
+        # NOTE: running the wgrad pair on a side stream under the
+        # dgrad was tried and measured WORSE (113.7 -> 114.7 ms
+        # epoch): the timeline is gap-free compute, so concurrent
+        # saturating kernels just share CUs plus event overhead.
+        # wgrad pair fused in one MFMA split-M kernel (g streamed
+        # once for both products; deterministic workspace reduce)
+        gw1, gw2 = native().dual_wgrad(g, x1.contiguous(), x2.contiguous())
+    else:
+        gw1 = g.t() @ x1
+        gw2 = g.t() @ x2
+    if not has_bias:
+        return gw1, gw2, None
+    gb = native().colsum(g)  # two-phase column sum (fastest measured)
+    return gw1, gw2, gb.to(w1.dtype)
+
+
+def _mm_dgrad(g, w):
+    """g @ w: the input gradient of one linear map through rocBLAS."""
+    return g @ w
+
+
+def _sage_dgrad(g, w1, w2, need1=True, need2=True):
+    """(g @ w1, g @ w2) for a contiguous g, None where need1 / need2 says
+    the gradient is not wanted. Every dgrad of the dual linear goes through
+    here, and nobody calls it with neither wanted."""
+    if g.is_cuda and g.dtype == torch.float32:
+        if g.size(1) >= 64 and w1.size(1) <= 256:
+            # dgrad pair fused in one MFMA kernel (g tile staged once
+            # for both weight contractions; measured par with rocBLAS
+            # at K=256 — 117 TF both; rocBLAS wins at K=512 (142 vs
+            # 123 TF) and K=602 (112 vs 95), hence the cap). It computes
+            # both whoever wants them.
+            gx1, gx2 = native().dual_dgrad(g, w1.contiguous(),
+                                           w2.contiguous())
+            return (gx1 if need1 else None), (gx2 if need2 else None)
+        if need1 and need2:
+            # thin-N (the 41-class output layer) and wide-K (602:
+            # rocBLAS 112 vs our 95 TF — the unaligned 602-float rows
+            # and boundary k-tile cost us there): ONE GEMM against
+            # [w1 ‖ w2] so g is still read once
+            gx = _mm_dgrad(g, torch.cat((w1, w2), dim=1))
+            K = w1.size(1)
+            return gx[:, :K], gx[:, K:]
+    return (_mm_dgrad(g, w1) if need1 else None,
+            _mm_dgrad(g, w2) if need2 else None)
+
+
+class _SageMeanLayer(torch.autograd.Function):
+    """The mean layer's training path as one node (docs/DESIGN.md, "Fused
+    layer backward"):
+
+        feat = dropout(h, p);  ah = D^{-1} A feat
+        out = feat[:num_in] @ w1^T + ah @ w2^T + (b1 + b2)
+
+    The forward is `fused_dropout`, `spmm_mean` and `sage_dual_linear` as
+    they are, in that order. The backward knows what the three separate
+    nodes cannot: that the self term's gradient and the dropout mask meet the
+    transpose SpMM's output element by element, so both ride in that
+    kernel's epilogue, and that an input without a gradient needs no dgrad
+    and no transpose at all."""
+
+    @staticmethod
+    def forward(ctx, graph: HaloGraph, h, inv_deg, w1, w2, b1, b2, p):
+        mask = None
+        feat = h
+        if p > 0:
+            # host-drawn 63-bit seed, as fused_dropout draws it
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+            feat, mask = native().dropout_fwd(h.contiguous(), p, seed)
+        ah = _spmm_mean_forward(graph, feat, inv_deg)
+        x1 = feat[: graph.num_in]
+        ctx.graph, ctx.p, ctx.has_bias = graph, p, b1 is not None
+        # The two activations are intermediates of this node (neither an
+        # input nor an output), kept on ctx so that the backward can let go
+        # of them after the wgrad, where the dual linear's own node released
+        # them: saved tensors live until the node has finished, which here is
+        # after the transpose SpMM, at the step's memory peak. With p == 0,
+        # x1 is a view of the input and goes the checked way.
+        ctx.acts = (ah,) if mask is None else (ah, x1)
+        ctx.save_for_backward(w1, w2, inv_deg, mask,
+                              *((x1,) if mask is None else ()))
+        return _sage_dual_forward(x1, ah, w1, w2, b1, b2)
+
+    @staticmethod
+    def backward(ctx, g):
+        w1, w2, inv_deg, mask, *saved_x1 = ctx.saved_tensors
+        if ctx.acts is None:
+            raise RuntimeError("sage_mean_layer: its activations are freed "
+                               "by the first backward; a second one through "
+                               "a retained graph is not supported")
+        ah, x1 = ctx.acts + tuple(saved_x1)
+        ctx.acts = None
+        g = g.contiguous()
+        gw1, gw2, gb = _sage_param_grads(g, x1, ah, w1, ctx.has_bias)
+        del ah, x1, saved_x1
+        gh = None
+        if ctx.needs_input_grad[1]:
+            gx1, gx2 = _sage_dgrad(g, w1, w2)
+            epilogue = dict(add_rows=gx1, n_add=ctx.graph.num_in)
+            if mask is not None:
+                epilogue.update(drop_mask=mask,
+                                drop_scale=dropout_scale(ctx.p))
+            gh = _spmm_mean_backward(ctx.graph, gx2, inv_deg, **epilogue)
+        return None, gh, None, gw1, gw2, gb, gb, None
+
+
+def sage_mean_layer(graph: HaloGraph, h: torch.Tensor,
+                    inv_deg: torch.Tensor, lin1, lin2,
+                    p: float = 0.0) -> torch.Tensor:
+    """`sage_dual_linear(feat[:num_in], spmm_mean(graph, feat, inv_deg),
+    lin1, lin2)` with `feat = fused_dropout(h, p)` (h itself when p == 0),
+    as one autograd node: same forward, same host seed draw, bitwise the
+    same output and gradients, a shorter backward. GPU tensors only."""
+    if not h.is_cuda:
+        raise ValueError("sage_mean_layer is the GPU path")
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"sage_mean_layer: p={p} is outside [0, 1)")
+    return _SageMeanLayer.apply(graph, h, inv_deg, lin1.weight, lin2.weight,
+                                lin1.bias, lin2.bias, p)
 
 
 def sage_dual_linear(x1, x2, lin1, lin2):
@@ -1101,7 +1243,9 @@ class _LinearColsum(torch.autograd.Function):
             (gw,) = native().dual_wgrad(g, x.contiguous(), torch.Tensor())
         else:
             gw = g.t() @ x
-        return g @ w, gw, gb
+        # a first layer's input is the constant features: no dgrad
+        gx = _mm_dgrad(g, w) if ctx.needs_input_grad[0] else None
+        return gx, gw, gb
 
 
 def linear(x, lin):

@@ -25,7 +25,12 @@ With --edge-drop it compares the masked kernel of edge dropout
 (csrc/hip/spmm_drop.hip) with the plain dense kernel, forward and transpose,
 at each rate and with every edge kept, alternating in the same rounds.
 
+With --epilogue it compares the transpose SpMM with and without the add /
+dropout epilogue of the fused layer backward, and times the eager accumulate
+and dropout_bwd passes the epilogue replaces.
+
 Usage (on a GPU box):
+    python -m pipegcn_amd.tools.spmm_bench --f 256 --epilogue
     python -m pipegcn_amd.tools.spmm_bench --f 256 --edge-drop 0.2 0.5 0.8
     python -m pipegcn_amd.tools.spmm_bench [--f 602 256] [--rounds 5]
     python -m pipegcn_amd.tools.spmm_bench --f 256 --density 0.25 0.5 1.0
@@ -331,6 +336,61 @@ def edge_drop_table(hg, inv, widths, rates, dtype, rounds, iters):
         del z, g, fns
 
 
+def epilogue_table(hg, widths, dtype, rounds, iters):
+    """The transpose SpMM of the layer backward, plain and with the add /
+    dropout epilogue, alternating in the same rounds with the two eager
+    passes the epilogue replaces (accumulate, dropout_bwd). Prints best ms
+    and checks the fused output bitwise against the three separate steps."""
+    from pipegcn_amd import native, ops
+
+    n = hg.num_all
+    csc = hg.csc
+    none = torch.Tensor()
+    scale = ops.dropout_scale(0.5)
+    print("    F | plain ms | epilogue ms | add + dropout_bwd ms |"
+          " epilogue - plain")
+    for F in widths:
+        g = torch.Generator(device="cuda").manual_seed(F)
+        feat = torch.randn(n, F, device="cuda", generator=g).to(dtype)
+        wide = torch.randn(n, 2 * F, device="cuda", generator=g).to(dtype)
+        add = wide[:, :F]  # as the cat-GEMM hands it over
+        _, mask = native().dropout_fwd(feat, 0.5, 1)
+
+        def plain():
+            return native().spmm(csc.indptr, csc.indices, feat, none, none,
+                                 csc.row_order, csc.num_rows)
+
+        def fused():
+            return native().spmm(csc.indptr, csc.indices, feat, none, none,
+                                 csc.row_order, csc.num_rows, None, add, n,
+                                 mask, scale)
+
+        base = plain()
+
+        def tail():
+            return native().dropout_bwd(base + add, mask, 0.5)
+
+        assert torch.equal(fused().view(torch.uint8),
+                           tail().view(torch.uint8)), \
+            f"F={F}: the epilogue differs from add + dropout_bwd"
+        best = {}
+        for _ in range(rounds):
+            for name, fn in (("plain", plain), ("fused", fused),
+                             ("tail", tail)):
+                fn()
+                torch.cuda.synchronize()
+                t0 = time.time()
+                for _ in range(iters):
+                    fn()
+                torch.cuda.synchronize()
+                t = (time.time() - t0) / iters * 1e3
+                best[name] = min(best.get(name, t), t)
+        print(f"{F:5d} | {best['plain']:8.2f} | {best['fused']:11.2f} |"
+              f" {best['tail']:20.3f} |"
+              f" {best['fused'] - best['plain']:+.3f}", flush=True)
+        del feat, wide, add, base
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--f", type=int, nargs="+", default=[602, 256])
@@ -363,6 +423,11 @@ def main():
                          "of the masked kernel, time the masked forward and "
                          "transpose against the plain dense kernel (--dtype "
                          "as given; fp32 adds the packed forward)")
+    ap.add_argument("--epilogue", action="store_true",
+                    help="instead of the lane-width A/B: the transpose SpMM "
+                         "plain and with the add / dropout epilogue of the "
+                         "fused layer backward, and the two eager passes it "
+                         "replaces")
     args = ap.parse_args()
 
     from pipegcn_amd import ops
@@ -372,6 +437,10 @@ def main():
     deg = hg.csr.row_degrees().to("cuda").clamp(min=1)
     inv = (1.0 / deg).contiguous()
     print(f"graph: {n} nodes, {E} edges")
+    if args.epilogue:
+        epilogue_table(hg, args.f, torch.bfloat16 if args.dtype == "bf16"
+                       else torch.float32, args.rounds, args.iters)
+        return
     if args.max:
         widths = args.f if args.f != ap.get_default("f") else [64, 256, 602]
         max_table(hg, E, widths, args.rounds, args.iters)
