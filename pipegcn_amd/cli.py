@@ -21,8 +21,8 @@ def create_parser(argv=None):
     parser.add_argument("--graph-name", "--graph_name", type=str, default="")
 
     parser.add_argument("--model", type=str, default="graphsage",
-                        help="model for training: graphsage, gcn, gat or "
-                             "gatv2")
+                        help="model for training: graphsage, gcn, gat, "
+                             "gatv2 or transformer")
     parser.add_argument("--dropout", type=float, default=0.5,
                         help="dropout probability")
     parser.add_argument("--lr", type=float, default=1e-2,
@@ -38,15 +38,17 @@ def create_parser(argv=None):
     parser.add_argument("--n-linear", "--n_linear", type=int, default=0,
                         help="the number of linear layers")
     parser.add_argument("--n-heads", "--n_heads", type=int, default=1,
-                        help="attention heads of the hidden GAT / GATv2 "
-                             "layers (--model gat, gatv2; must divide "
-                             "--n-hidden; extension over the reference)")
+                        help="attention heads of the hidden GAT / GATv2 / "
+                             "transformer layers (--model gat, gatv2, "
+                             "transformer; must divide --n-hidden; "
+                             "extension over the reference)")
     parser.add_argument("--attn-drop", "--attn_drop", type=float,
                         default=0.0,
-                        help="attention dropout of the GAT / GATv2 layers: "
-                             "probability in [0, 1) of dropping an edge's "
-                             "attention coefficient, per head, in training "
-                             "(--model gat, gatv2)")
+                        help="attention dropout of the GAT / GATv2 / "
+                             "transformer layers: probability in [0, 1) of "
+                             "dropping an edge's attention coefficient, per "
+                             "head, in training (--model gat, gatv2, "
+                             "transformer)")
     parser.add_argument("--edge-drop", "--edge_drop", type=_edge_drop_rate,
                         default=0.0,
                         help="edge dropout (DropEdge) of the GraphSAGE-mean "
@@ -54,7 +56,8 @@ def create_parser(argv=None):
                              "removing an edge, redrawn per layer and step "
                              "in training, the kept sum scaled by 1/(1-p) "
                              "over the full-graph degrees (--model "
-                             "graphsage with --aggregator mean, gcn)")
+                             "graphsage with --aggregator mean, gcn; "
+                             "refused with gat, gatv2 and transformer)")
     parser.add_argument("--aggregator", choices=["mean", "pool"],
                         default="mean",
                         help="neighbourhood aggregator of the GraphSAGE "

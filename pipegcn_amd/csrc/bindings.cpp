@@ -334,5 +334,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("num_cols"), py::arg("num_heads"), py::arg("slope"),
         py::arg("drop_key") = 0, py::arg("drop_thr") = 0,
         py::arg("drop_scale") = 1.0);
+  m.def("dot_fwd", &dot_fwd_hip,
+        "dot-product attention aggregation over the CSR -> (agg, lse); kv is "
+        "[nodes, 2F] = [K | V], lse in natural-log units",
+        py::arg("indptr"), py::arg("indices"), py::arg("q"), py::arg("kv"),
+        py::arg("row_order"), py::arg("num_cols"), py::arg("num_heads"),
+        py::arg("scale"), py::arg("drop_key") = 0, py::arg("drop_thr") = 0,
+        py::arg("drop_scale") = 1.0);
+  m.def("dot_bwd_dst", &dot_bwd_dst_hip,
+        "dot-product attention backward over the CSR -> d_q",
+        py::arg("indptr"), py::arg("indices"), py::arg("g"), py::arg("q"),
+        py::arg("kv"), py::arg("lse"), py::arg("t"), py::arg("row_order"),
+        py::arg("num_cols"), py::arg("num_heads"), py::arg("scale"),
+        py::arg("drop_key") = 0, py::arg("drop_thr") = 0,
+        py::arg("drop_scale") = 1.0);
+  m.def("dot_bwd_src", &dot_bwd_src_hip,
+        "dot-product attention backward over the CSC -> d_kv [nodes, 2F]",
+        py::arg("indptr"), py::arg("indices"), py::arg("g"), py::arg("q"),
+        py::arg("kv"), py::arg("lse"), py::arg("t"), py::arg("row_order"),
+        py::arg("num_cols"), py::arg("num_heads"), py::arg("scale"),
+        py::arg("drop_key") = 0, py::arg("drop_thr") = 0,
+        py::arg("drop_scale") = 1.0);
   m.attr("with_hip") = true;
 }

@@ -258,6 +258,35 @@ torch::Tensor gatv2_bwd_src_hip(
     torch::Tensor t, torch::Tensor row_order, int64_t num_cols, int64_t H,
     double slope, int64_t drop_key, int64_t drop_thr, double drop_scale);
 
+// Scaled dot-product attention aggregation (csrc/hip/dot_attn.hip):
+//   s_uvh = scale * <q[v,h,:], K[u,h,:]>, alpha = softmax_u(s),
+//   agg[v] = sum_u w * alpha * V[u,h,:],
+// with K = kv[:, :F] and V = kv[:, F:] the halves of one [nodes, 2F] record
+// (this layout is the op's contract). Every pass recomputes s from the
+// gathered rows; nothing of size nnz is allocated. q/g/agg/d_q are fp32 or
+// bf16 [nodes, F] with F = H * D and D <= 1024, kv/d_kv are [nodes, 2F] of
+// the same dtype; lse/t are fp32 [nodes, H], lse in natural-log units. The
+// drop_* arguments are those of gat_aggregate_fwd_hip (drop_thr == 0: no
+// dropout). -> {agg, lse}; rows without edges get 0 and 0.
+std::vector<torch::Tensor> dot_fwd_hip(
+    torch::Tensor indptr, torch::Tensor indices, torch::Tensor q,
+    torch::Tensor kv, torch::Tensor row_order, int64_t num_cols, int64_t H,
+    double scale, int64_t drop_key, int64_t drop_thr, double drop_scale);
+// Destination-side backward over the CSR, t[v,h] = g[v,h,:] . agg[v,h,:].
+// -> d_q [num_rows, F].
+torch::Tensor dot_bwd_dst_hip(
+    torch::Tensor indptr, torch::Tensor indices, torch::Tensor g,
+    torch::Tensor q, torch::Tensor kv, torch::Tensor lse, torch::Tensor t,
+    torch::Tensor row_order, int64_t num_cols, int64_t H, double scale,
+    int64_t drop_key, int64_t drop_thr, double drop_scale);
+// Source-side backward; indptr/indices/row_order are the CSC (rows =
+// sources, num_cols = destinations). -> d_kv [num_rows, 2F] = [d_K | d_V].
+torch::Tensor dot_bwd_src_hip(
+    torch::Tensor indptr, torch::Tensor indices, torch::Tensor g,
+    torch::Tensor q, torch::Tensor kv, torch::Tensor lse, torch::Tensor t,
+    torch::Tensor row_order, int64_t num_cols, int64_t H, double scale,
+    int64_t drop_key, int64_t drop_thr, double drop_scale);
+
 // Fused dual GEMM for the GraphSAGE layer forward:
 //   out[M,N] = x1[M,K] @ w1[N,K]^T + x2[M,K] @ w2[N,K]^T + bias[N]
 // fp32, MFMA (v_mfma_f32_32x32x2_f32). Weights in torch Linear layout [N,K],

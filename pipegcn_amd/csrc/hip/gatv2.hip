@@ -28,14 +28,11 @@
 // keep(key, u, v, h) / (1 - p) from gat.hip's endpoint hash (attn_util.h);
 // the softmax itself (lse) is never masked.
 //
-// Lane layout. A head's D features are cut into G = D / VEC groups of VEC
-// elements (VEC | D: one lane access is one aligned 4..16-byte load). A wave
-// is split into 64 / SEG segments of SEG lanes; each segment owns one head
-// and lane sl of it holds groups sl, sl + SEG, ... (NV of them), so a wave's
-// loads of one row are contiguous. SEG < 64 packs 8, 4 or 2 narrow heads
-// (G <= 8, 16, 32) into a wave; the dot is a butterfly over SEG lanes: DPP
-// exchanges inside a row of 16 lanes, shuffles across rows. Heads up to
-// 64 * NV * VEC <= 1024 wide fit; launchers refuse wider ones.
+// Lane layout (attn_lanes.h, shared with dot_attn.hip): a head's D features
+// are cut into groups of VEC elements, a wave into 64 / SEG segments of SEG
+// lanes that own one head each, NV groups per lane; the dot is a butterfly
+// over SEG lanes. Heads up to 64 * NV * VEC <= 1024 wide fit; launchers
+// refuse wider ones.
 //
 // One fixed set of lanes walks a row's edges in CSR/CSC order and all
 // reductions are fixed-order butterflies: results are bitwise reproducible
@@ -47,6 +44,7 @@
 // lane) run at reduced occupancy by their register count alone.
 
 #include "../common.h"
+#include "attn_lanes.h"
 #include "attn_util.h"
 #include "hip_util.h"
 
@@ -60,134 +58,10 @@
 namespace {
 
 // ld_vec / st_vec, leaky, the drop_* hash, wave_ids, for_edges and the
-// host-side input checks are shared with gat.hip
-using namespace attn_util;
-
-// finite stand-in for -inf: exp(kNegBig - s) is 0, not NaN
-constexpr float kNegBig = -1e30f;
-// widest head the lane layout holds: 64 lanes x 16 elements
-constexpr int64_t kMaxHeadDim = 1024;
-
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-
-// edges whose gathered rows are in flight together: four at up to 4 elements
-// per lane (as the SpMM), fewer when a lane already issues 8 or 16 loads
-template <int E>
-constexpr int kUnroll = E <= 4 ? 4 : (E <= 8 ? 2 : 1);
-
-// One DPP lane exchange inside a row of 16 lanes: a VALU operand modifier,
-// not an LDS round trip like __shfl_xor's ds_bpermute.
-template <int CTRL>
-__device__ __forceinline__ float dpp(float x) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(
-      0, __float_as_int(x), CTRL, 0xF, 0xF, true));
-}
-constexpr int kQuadXor1 = 0xB1;     // quad_perm [1,0,3,2]
-constexpr int kQuadXor2 = 0x4E;     // quad_perm [2,3,0,1]
-constexpr int kHalfMirror = 0x141;  // lane i <- lane 7 - i of its 8
-constexpr int kRowMirror = 0x140;   // lane i <- lane 15 - i of its 16
-
-// Fixed-order sum over 8 lanes: after the two quad steps a quad's lanes
-// agree, so the mirror partner carries the other quad's sum.
-__device__ __forceinline__ float oct_sum(float x) {
-  x += dpp<kQuadXor1>(x);
-  x += dpp<kQuadXor2>(x);
-  x += dpp<kHalfMirror>(x);
-  return x;
-}
-
-// fixed-order sum over the SEG lanes of a segment: every lane of it ends
-// with the same total. Rows of 16 reduce by DPP, rows combine by shuffles.
-template <int SEG>
-__device__ __forceinline__ float seg_sum(float x) {
-  x = oct_sum(x);
-  if constexpr (SEG >= 16) x += dpp<kRowMirror>(x);
-#pragma unroll
-  for (int off = 16; off < SEG; off <<= 1) x += __shfl_xor(x, off, kWave);
-  return x;
-}
-
-// Two segment sums for the price of one plus two exchanges: the first step
-// leaves a's partial sums in the lower half of the segment and b's in the
-// upper half, the halves reduce separately, the last step swaps the totals.
-template <int SEG>
-__device__ __forceinline__ void seg_sum2(float& a, float& b, int lane) {
-  const bool hi = lane & (SEG / 2);
-  float keep = hi ? b : a;
-  const float send = hi ? a : b;
-  float other;
-  if constexpr (SEG == 8) {
-    keep += dpp<kHalfMirror>(send);
-    keep += dpp<kQuadXor1>(keep);
-    keep += dpp<kQuadXor2>(keep);
-    other = dpp<kHalfMirror>(keep);
-  } else if constexpr (SEG == 16) {
-    keep += dpp<kRowMirror>(send);
-    keep = oct_sum(keep);
-    other = dpp<kRowMirror>(keep);
-  } else {
-    keep += __shfl_xor(send, SEG / 2, kWave);
-    keep = seg_sum<SEG / 2>(keep);
-    other = __shfl_xor(keep, SEG / 2, kWave);
-  }
-  a = hi ? other : keep;
-  b = hi ? keep : other;
-}
-
-// Where this lane's NV groups of head `h` start inside a [*, F] row, and
-// which of them exist. A lane of a segment whose head is past H owns nothing
-// but still takes part in the butterflies.
-template <int VEC, int NV, int SEG>
-struct LaneMap {
-  int off[NV];
-  bool ok[NV];
-  int64_t h;  // clamped to a valid head for the per-head scalar loads
-  bool head_ok;
-
-  __device__ __forceinline__ LaneMap(int lane, int64_t hgroup, int64_t H,
-                                     int64_t D) {
-    const int sl = lane & (SEG - 1);
-    h = hgroup * (kWave / SEG) + lane / SEG;
-    head_ok = h < H;
-    if (!head_ok) h = H - 1;
-    const int G = static_cast<int>(D / VEC);
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-      const int grp = k * SEG + sl;
-      ok[k] = head_ok && grp < G;
-      off[k] = static_cast<int>(h * D) + (ok[k] ? grp : 0) * VEC;
-    }
-  }
-};
-
-// this lane's E = NV * VEC elements of one row; groups it does not own are 0
-template <typename T, int VEC, int NV, int SEG>
-__device__ __forceinline__ void ld_row(const T* row,
-                                       const LaneMap<VEC, NV, SEG>& lm,
-                                       float (&v)[NV * VEC]) {
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-    float t[VEC];
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) t[j] = 0.f;
-    if (lm.ok[k]) ld_vec<T, VEC>(row + lm.off[k], t);
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) v[k * VEC + j] = t[j];
-  }
-}
-
-template <typename T, int VEC, int NV, int SEG>
-__device__ __forceinline__ void st_row(T* row,
-                                       const LaneMap<VEC, NV, SEG>& lm,
-                                       const float (&v)[NV * VEC]) {
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-    float t[VEC];
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) t[j] = v[k * VEC + j];
-    if (lm.ok[k]) st_vec<T, VEC>(row + lm.off[k], t);
-  }
-}
+// host-side input checks are shared with gat.hip (attn_util.h); the segment
+// butterflies, LaneMap, ld_row / st_row, kUnroll and the launch glue with
+// dot_attn.hip (attn_lanes.h)
+using namespace attn_lanes;
 
 // ---------------------------------------------------------------------------
 // Forward over the CSR: out[r,h,:] = sum_e w * alpha * zl[u_e,h,:] and
@@ -455,107 +329,22 @@ void check_attn(const torch::Tensor& attn, int64_t H, int64_t D) {
               "] tensor");
 }
 
-// The lane layout of one head width (file header). 4-element accesses need
-// D % 4 == 0, 16-byte (fp32) / 8-byte (bf16) aligned bases and at least 8
-// groups (the narrowest segment); narrower heads fill their segment with
-// single elements instead.
-struct Layout {
-  int vec, nv, seg;
-};
-
-Layout pick_layout(int64_t D, int64_t elem_size, const torch::Tensor& attn,
-                   std::initializer_list<const void*> ptrs) {
-  TORCH_CHECK(D >= 1 && D <= kMaxHeadDim, "gatv2: head width D=", D,
-              " exceeds the supported ", kMaxHeadDim);
-  bool wide = D % 4 == 0 && D >= 32 && aligned_to(attn.data_ptr(), 16);
-  for (const void* p : ptrs) wide = wide && aligned_to(p, 4 * elem_size);
-  Layout l;
-  l.vec = wide ? 4 : 1;
-  const int64_t G = D / l.vec;
-  l.seg = G <= 8 ? 8 : (G <= 16 ? 16 : (G <= 32 ? 32 : 64));
-  if (l.vec == 1 && l.seg == 8) l.seg = 16;  // 1-wide: compiled from 16 up
-  l.nv = 1;
-  while (static_cast<int64_t>(l.nv) * kWave < G) l.nv *= 2;
-  return l;
-}
-
-// fn(VEC, NV, SEG as integral constants) for the compiled layouts
-template <typename Fn>
-void dispatch_layout(const Layout& l, Fn&& fn) {
-#define GATV2_CASE(V, N, S)                                      \
-  if (l.vec == V && l.nv == N && l.seg == S) {                   \
-    fn(std::integral_constant<int, V>{},                         \
-       std::integral_constant<int, N>{},                         \
-       std::integral_constant<int, S>{});                        \
-    return;                                                      \
-  }
-  GATV2_CASE(1, 1, 16)
-  GATV2_CASE(1, 1, 32)
-  GATV2_CASE(1, 1, 64)
-  GATV2_CASE(1, 2, 64)
-  GATV2_CASE(1, 4, 64)
-  GATV2_CASE(1, 8, 64)
-  GATV2_CASE(1, 16, 64)
-  GATV2_CASE(4, 1, 8)
-  GATV2_CASE(4, 1, 16)
-  GATV2_CASE(4, 1, 32)
-  GATV2_CASE(4, 1, 64)
-  GATV2_CASE(4, 2, 64)
-  GATV2_CASE(4, 4, 64)
-#undef GATV2_CASE
-  TORCH_CHECK(false, "gatv2: no kernel for layout vec=", l.vec,
-              " nv=", l.nv, " seg=", l.seg);
-}
-
-template <typename T>
-const T* cptr(const torch::Tensor& x) {
-  return reinterpret_cast<const T*>(x.data_ptr());
-}
-template <typename T>
-T* mptr(torch::Tensor& x) {
-  return reinterpret_cast<T*>(x.data_ptr());
-}
-
-// fn(T{}) for the element type T of x (fp32 or bf16: check_features)
-template <typename Fn>
-void dispatch_dtype(const torch::Tensor& x, Fn&& fn) {
-  if (x.scalar_type() == torch::kBFloat16)
-    fn(__hip_bfloat16{});
-  else
-    fn(float{});
-}
-
 // One launch of a wave-per-(row, head group) kernel over `indptr`'s rows:
-// the lane layout from the head width and the alignment of `ptrs`, the grid,
-// the launch and its check. kernel_of(VEC, NV, SEG as integral constants)
-// returns the instance; `mid` are the kernel's arguments between the graph
-// and the sizes (the three kernels share what comes before and after).
+// the lane layout from the head width and the alignment of attn and `ptrs`,
+// then attn_lanes::launch. `mid` are the kernel's arguments between the
+// graph and the sizes (the three kernels share what comes before and after).
 template <typename KernelOf, typename... Mid>
-void launch(const torch::Tensor& indptr, const torch::Tensor& indices,
-            const torch::Tensor& zl, int64_t H, const torch::Tensor& attn,
-            std::initializer_list<const void*> ptrs, float slope,
-            DropArgs drop, KernelOf&& kernel_of, Mid... mid) {
-  const int64_t num_rows = indptr.numel() - 1, F = zl.size(1), D = F / H;
-  const Layout l = pick_layout(D, zl.element_size(), attn, ptrs);
-  dispatch_layout(l, [&](auto vec_c, auto nv_c, auto seg_c) {
-    constexpr int SEG = decltype(seg_c)::value;
-    const int64_t hpw = kWave / SEG, nhg = (H + hpw - 1) / hpw;
-    const int threads = 256;
-    hipLaunchKernelGGL(kernel_of(vec_c, nv_c, seg_c),
-                       dim3(grid_for(num_rows * nhg, threads)), dim3(threads),
-                       0, current_stream(), indptr.data_ptr<int64_t>(),
-                       indices.data_ptr<int32_t>(), mid..., num_rows, F, H, D,
-                       nhg, slope, drop.key, drop.thr, drop.scale);
-  });
-  check_launch();
+void launch_v2(const torch::Tensor& indptr, const torch::Tensor& indices,
+               const torch::Tensor& zl, int64_t H, const torch::Tensor& attn,
+               std::initializer_list<const void*> ptrs, float slope,
+               DropArgs drop, KernelOf&& kernel_of, Mid... mid) {
+  const int64_t F = zl.size(1);
+  const Layout l =
+      pick_layout(kOp, F / H, zl.element_size(), attn.data_ptr(), ptrs);
+  launch(kOp, l, indptr, indices, F, H, slope, drop, kernel_of, mid...);
 }
 
-// kernel_of for launch(): the <T, VEC, NV, SEG> instance of a kernel template
-#define GATV2_KERNEL_OF(kernel, T)                                     \
-  [](auto vec_c, auto nv_c, auto seg_c) {                              \
-    return kernel<T, decltype(vec_c)::value, decltype(nv_c)::value,    \
-                  decltype(seg_c)::value>;                             \
-  }
+#define GATV2_KERNEL_OF ATTN_LANES_KERNEL_OF
 
 }  // namespace
 
@@ -578,7 +367,7 @@ std::vector<torch::Tensor> gatv2_fwd_hip(
   if (num_rows == 0) return {out, lse};
   dispatch_dtype(zl, [&](auto tag) {
     using T = decltype(tag);
-    launch(indptr, indices, zl, H, attn,
+    launch_v2(indptr, indices, zl, H, attn,
            {zl.data_ptr(), zr.data_ptr(), out.data_ptr()},
            static_cast<float>(slope), drop,
            GATV2_KERNEL_OF(gatv2_fwd_kernel, T), cptr<T>(zl), cptr<T>(zr),
@@ -610,7 +399,7 @@ std::vector<torch::Tensor> gatv2_bwd_dst_hip(
   if (num_rows == 0) return {d_zr, pa};
   dispatch_dtype(zl, [&](auto tag) {
     using T = decltype(tag);
-    launch(indptr, indices, zl, H, attn,
+    launch_v2(indptr, indices, zl, H, attn,
            {zl.data_ptr(), zr.data_ptr(), g.data_ptr(), d_zr.data_ptr()},
            static_cast<float>(slope), drop,
            GATV2_KERNEL_OF(gatv2_bwd_dst_kernel, T), cptr<T>(g), cptr<T>(zl),
@@ -649,7 +438,7 @@ torch::Tensor gatv2_bwd_src_hip(
   TORCH_CHECK(aligned_to(dst_state.data_ptr(), 8));
   dispatch_dtype(zl, [&](auto tag) {
     using T = decltype(tag);
-    launch(indptr, indices, zl, H, attn,
+    launch_v2(indptr, indices, zl, H, attn,
            {zl.data_ptr(), zr.data_ptr(), g.data_ptr(), d_zl.data_ptr()},
            static_cast<float>(slope), drop,
            GATV2_KERNEL_OF(gatv2_bwd_src_kernel, T), cptr<T>(g), cptr<T>(zl),

@@ -934,6 +934,153 @@ def gatv2_aggregate_csr(csr: CSR, zl: torch.Tensor, zr: torch.Tensor,
                                   slope)[0]
 
 
+# widest head every instance of csrc/hip/dot_attn.hip compiles to without
+# scratch (profiles/README.md): the full width of the lane layout
+DOT_MAX_HEAD_DIM = 1024
+
+
+def _dot_check(csr: CSR, q, kv, num_heads: int) -> None:
+    """Shape guards shared by both dot-attention paths; raised before any
+    launch."""
+    if num_heads < 1 or q.dim() != 2 or q.shape[1] % num_heads != 0:
+        raise ValueError(
+            f"dot_aggregate: feature width {tuple(q.shape)} is not "
+            f"num_heads*D for num_heads={num_heads}")
+    if kv.dim() != 2 or kv.shape[1] != 2 * q.shape[1] or kv.dtype != q.dtype:
+        raise ValueError(
+            f"dot_aggregate: kv must be [nodes, 2F] = [K | V] of q's dtype, "
+            f"got {tuple(kv.shape)} {kv.dtype} for q {tuple(q.shape)} "
+            f"{q.dtype}")
+    if kv.shape[0] < csr.num_cols:
+        raise ValueError(
+            f"dot_aggregate: kv has {kv.shape[0]} rows but the graph "
+            f"references {csr.num_cols} source nodes (an under-sized tensor "
+            "would be an out-of-bounds GPU gather)")
+    if q.shape[0] != csr.num_rows:
+        raise ValueError(
+            f"dot_aggregate: q has {q.shape[0]} rows, the graph has "
+            f"{csr.num_rows} destination nodes")
+    head_dim = q.shape[1] // num_heads
+    if q.is_cuda and head_dim > DOT_MAX_HEAD_DIM:
+        raise ValueError(
+            f"dot_aggregate: head width {head_dim} exceeds the kernels' "
+            f"{DOT_MAX_HEAD_DIM}")
+
+
+def _dot_scale(q, num_heads: int, scale: Optional[float]) -> float:
+    return float(scale) if scale is not None else (
+        1.0 / math.sqrt(q.shape[1] // num_heads))
+
+
+def _dot_aggregate_torch(csr: CSR, q, kv, num_heads: int, scale: float,
+                         drop=None):
+    """Dot-product attention aggregation composed from torch ops under
+    ordinary autograd: the CPU test tier and rank-0 eval. [nnz, H, D]
+    temporaries are fine here; the GPU path never makes them. drop = (key,
+    thr, scale) applies the attention-dropout mask the kernels would draw."""
+    u, v = _edge_endpoints(csr)
+    feats = q.shape[1]
+    kvf = kv.float()
+    ku = kvf[:, :feats].reshape(kv.shape[0], num_heads, -1).index_select(0, u)
+    vu = kvf[:, feats:].reshape(kv.shape[0], num_heads, -1).index_select(0, u)
+    qv = q.float().view(csr.num_rows, num_heads, -1).index_select(0, v)
+    s = (qv * ku).sum(-1) * scale
+    return _edge_softmax_aggregate_torch(csr, u, v, s, vu, drop).to(q.dtype)
+
+
+def _dot_forward_hip(csr: CSR, q, kv, num_heads, scale, drop=(0, 0, 1.0)):
+    """One gather pass on the gfx950 kernel -> (agg, lse). Uses
+    csr.row_order as given. drop = (key, thr, scale); thr 0 is no attention
+    dropout."""
+    return native().dot_fwd(csr.indptr, csr.indices, q, kv, _row_order(csr),
+                            csr.num_cols, num_heads, scale, *drop)
+
+
+class _DotAggregate(torch.autograd.Function):
+    """agg[v] = sum_u softmax_u(scale * <q[v], K[u]>) V[u] per head, with
+    kv = [K | V].
+
+    Saves per-node tensors only (q, kv, lse, agg). The backward is two
+    gather passes that recompute the score per edge: over the CSR for d_q,
+    over the CSC for d_kv (one [nodes, 2F] tensor, so the projection behind
+    kv has one backward GEMM). Attention dropout adds three scalars and no
+    tensor.
+    """
+
+    @staticmethod
+    def forward(ctx, graph: HaloGraph, q, kv, num_heads, scale, drop):
+        agg, lse = _dot_forward_hip(graph.csr, q, kv, num_heads, scale, drop)
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(q, kv, lse, agg)
+        ctx.graph, ctx.num_heads, ctx.scale = graph, num_heads, scale
+        ctx.drop = drop
+        return agg
+
+    @staticmethod
+    def backward(ctx, g):
+        q, kv, lse, agg = ctx.saved_tensors
+        csr, csc, H = ctx.graph.csr, ctx.graph.csc, ctx.num_heads
+        g = g.contiguous()
+        n = g.shape[0]
+        # per-node per-head dot: an elementwise pass over [num_in, F]
+        t = (g.view(n, H, -1).float() * agg.view(n, H, -1).float()).sum(-1)
+
+        d_q = native().dot_bwd_dst(
+            csr.indptr, csr.indices, g, q, kv, lse, t, _row_order(csr),
+            csr.num_cols, H, ctx.scale, *ctx.drop)
+        d_kv = native().dot_bwd_src(
+            csc.indptr, csc.indices, g, q, kv, lse, t, _row_order(csc),
+            csc.num_cols, H, ctx.scale, *ctx.drop)
+        if d_kv.shape[0] < kv.shape[0]:  # rows the graph never references
+            d_kv = torch.cat((d_kv, d_kv.new_zeros(
+                kv.shape[0] - d_kv.shape[0], d_kv.shape[1])))
+        return None, d_q, d_kv, None, None, None
+
+
+def dot_aggregate(graph: HaloGraph, q: torch.Tensor, kv: torch.Tensor,
+                  num_heads: int, scale: Optional[float] = None,
+                  attn_drop: float = 0.0,
+                  seed: Optional[int] = None) -> torch.Tensor:
+    """Differentiable scaled dot-product attention aggregation (UniMP's
+    TransformerConv without gate and edge features) over the halo graph.
+
+    q [num_in, H*D] are the destination-side queries; kv [num_all, 2*H*D]
+    holds, per local node, the key K = kv[:, :H*D] and the value V =
+    kv[:, H*D:] (this layout is the op's contract). The score of edge u -> v
+    and head h is scale * <q[v,h], K[u,h]>, softmaxed over the sources of v;
+    scale defaults to 1 / sqrt(D). Returns agg [num_in, H*D] = sum_u alpha_uv
+    V[u]; rows without edges are 0. Nothing of size nnz is allocated on the
+    GPU path, forward or backward (docs/DESIGN.md); heads wider than
+    DOT_MAX_HEAD_DIM are refused there.
+
+    attn_drop and seed are those of `gat_aggregate`: the same endpoint hash
+    (`gat_dropout_keep`), applied after the softmax, recomputed in every
+    pass; attn_drop == 0 draws nothing from the generator.
+    """
+    drop = _attn_dropout("dot_aggregate", attn_drop, seed)
+    _dot_check(graph.csr, q, kv, num_heads)
+    scale = _dot_scale(q, num_heads, scale)
+    if not q.is_cuda:
+        return _dot_aggregate_torch(graph.csr, q, kv, num_heads, scale,
+                                    drop if drop[1] > 0 else None)
+    return _DotAggregate.apply(graph, q.contiguous(), kv.contiguous(),
+                               num_heads, scale, drop)
+
+
+def dot_aggregate_csr(csr: CSR, q: torch.Tensor, kv: torch.Tensor,
+                      num_heads: int,
+                      scale: Optional[float] = None) -> torch.Tensor:
+    """Forward-only dot-product attention aggregation over a plain CSR
+    (full-graph eval over FullGraph.csr); never drops."""
+    _dot_check(csr, q, kv, num_heads)
+    scale = _dot_scale(q, num_heads, scale)
+    with torch.no_grad():
+        if not q.is_cuda:
+            return _dot_aggregate_torch(csr, q, kv, num_heads, scale)
+        return _dot_forward_hip(csr, q.contiguous(), kv.contiguous(),
+                                num_heads, scale)[0]
+
+
 class _BiasColsum(torch.autograd.Function):
     """x + b with the bias gradient through the native colsum (see
     sage_dual_linear: torch's own reduce is pathological for thin odd N)."""

@@ -177,8 +177,8 @@ def create_model(layer_size, args):
     aggregator = getattr(args, "aggregator", "mean")
     edge_drop = getattr(args, "edge_drop", 0.0)
     if edge_drop > 0 and (aggregator == "pool"
-                          or args.model in ("gat", "gatv2")):
-        # a masked max gather is a later item; GAT has --attn-drop
+                          or args.model in ("gat", "gatv2", "transformer")):
+        # a masked max gather is a later item; attention has --attn-drop
         what = ("--aggregator pool" if aggregator == "pool"
                 else f"--model {args.model}")
         raise NotImplementedError(
@@ -213,6 +213,14 @@ def create_model(layer_size, args):
                      train_size=args.n_train,
                      n_heads=getattr(args, "n_heads", 1),
                      attn_drop=getattr(args, "attn_drop", 0.0))
+    if args.model == "transformer":
+        from pipegcn_amd.models.transformer import Transformer
+
+        return Transformer(layer_size, F.relu, args.use_pp, norm=args.norm,
+                           dropout=args.dropout, n_linear=args.n_linear,
+                           train_size=args.n_train,
+                           n_heads=getattr(args, "n_heads", 1),
+                           attn_drop=getattr(args, "attn_drop", 0.0))
     raise NotImplementedError(f"unknown model {args.model}")
 
 

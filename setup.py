@@ -31,6 +31,7 @@ ext = CUDAExtension(
         "pipegcn_amd/csrc/hip/dual_dgrad.hip",
         "pipegcn_amd/csrc/hip/gat.hip",
         "pipegcn_amd/csrc/hip/gatv2.hip",
+        "pipegcn_amd/csrc/hip/dot_attn.hip",
     ],
     extra_compile_args={
         # -fopenmp: at::parallel_for is a header template — its OpenMP

@@ -24,7 +24,14 @@ in the same rounds: gatv2_fwd, gatv2_bwd_dst (CSR pass), gatv2_bwd_src (CSC
 pass), ops.gatv2_aggregate forward and forward+backward, and GATv2 with 4
 heads under `--epoch`.
 
+`--dot` adds the dot-product attention kernels (csrc/hip/dot_attn.hip) the
+same way: dot_fwd, dot_bwd_dst (CSR pass), dot_bwd_src (CSC pass) and
+ops.dot_aggregate forward and forward+backward, with kv = [K | V] of width
+2F. With `--v2` its table also sets them against the GATv2 rows of the same
+rounds.
+
     python tools/microbench/gat_bench.py [--shape reddit] [--feats 256]
+    python tools/microbench/gat_bench.py --v2 --dot
     python tools/microbench/gat_bench.py --epoch
     python tools/microbench/gat_bench.py [--epoch] --attn-drop 0.6
 `--pool` adds GraphSAGE with the max-pooling aggregator (csrc/hip/
@@ -64,6 +71,8 @@ ap.add_argument("--attn-drop", "--attn_drop", type=float, default=0.0,
                 help="attention dropout of every GAT call (default: none)")
 ap.add_argument("--v2", action="store_true",
                 help="also time the GATv2 kernels / model")
+ap.add_argument("--dot", action="store_true",
+                help="also time the dot-product attention kernels")
 ap.add_argument("--pool", action="store_true",
                 help="with --epoch: also time GraphSAGE with the max-pooling "
                      "aggregator")
@@ -284,6 +293,38 @@ for dname in args.dtypes:
                     hg, z, zr2, attn, H, SLOPE, args.attn_drop, DROP_SEED),
                 "v2_fwd_bwd": v2_fb,
             })
+        if args.dot:
+            # q on the dst rows, kv = [K | V] records on all rows
+            q = torch.randn(rp.num_in, F, device=dev, generator=gen).to(dtype)
+            kv = torch.randn(rp.num_all, 2 * F, device=dev,
+                             generator=gen).to(dtype)
+            c = (F // H) ** -0.5
+            agg3, lse3 = nat.dot_fwd(csr.indptr, csr.indices, q, kv, ro,
+                                     csr.num_cols, H, c)
+            t3 = (g.view(-1, H, F // H).float()
+                  * agg3.view(-1, H, F // H).float()).sum(-1)
+            qr = q.clone().requires_grad_(True)
+            kvr = kv.clone().requires_grad_(True)
+
+            def dot_fb():
+                qr.grad = kvr.grad = None
+                ops.dot_aggregate(hg, qr, kvr, H, None, args.attn_drop,
+                                  DROP_SEED).backward(g)
+
+            fns.update({
+                "dot_fwd_k": lambda: nat.dot_fwd(
+                    csr.indptr, csr.indices, q, kv, ro, csr.num_cols, H, c,
+                    *drop),
+                "dot_bwd_dst": lambda: nat.dot_bwd_dst(
+                    csr.indptr, csr.indices, g, q, kv, lse3, t3, ro,
+                    csr.num_cols, H, c, *drop),
+                "dot_bwd_src": lambda: nat.dot_bwd_src(
+                    csc.indptr, csc.indices, g, q, kv, lse3, t3, roc,
+                    csc.num_cols, H, c, *drop),
+                "dot_fwd": lambda: ops.dot_aggregate(
+                    hg, q, kv, H, None, args.attn_drop, DROP_SEED),
+                "dot_fwd_bwd": dot_fb,
+            })
         ms = bench(fns)
         # logical bytes per edge: index + gathered row (+ per-head scalars);
         # the bwd gathers one packed 16 B (er, lse, t, 0) per edge and head
@@ -294,6 +335,12 @@ for dname in args.dtypes:
             # the CSC pass gathers two rows (g, zr) and 8 B (lse, t) per head
             per_edge.update({"v2_fwd_k": es * F + 4, "v2_bwd_dst": es * F + 4,
                              "v2_bwd_src": 2 * es * F + 8 * H + 4})
+        if args.dot:
+            # both CSR passes gather the 2F record; the CSC pass two rows
+            # (q, g) and 8 B (lse, t) per head
+            per_edge.update({"dot_fwd_k": 2 * es * F + 4,
+                             "dot_bwd_dst": 2 * es * F + 4,
+                             "dot_bwd_src": 2 * es * F + 8 * H + 4})
         rec = dict(dtype=dname, H=H, F=F, nnz=nnz, attn_drop=args.attn_drop,
                    ms={k: round(v, 3) for k, v in ms.items()},
                    tb_per_s={k: round(nnz * b / ms[k] / 1e9, 3)
@@ -305,6 +352,10 @@ for dname in args.dtypes:
             rec["v2_fwd_ratio"] = round(ms["v2_fwd"] / ms["spmm_fwd"], 3)
             rec["v2_fwd_bwd_ratio"] = round(ms["v2_fwd_bwd"]
                                             / ms["spmm_fwd_bwd"], 3)
+        if args.dot:
+            rec["dot_fwd_ratio"] = round(ms["dot_fwd"] / ms["spmm_fwd"], 3)
+            rec["dot_fwd_bwd_ratio"] = round(ms["dot_fwd_bwd"]
+                                             / ms["spmm_fwd_bwd"], 3)
         print(json.dumps(rec), flush=True)
         rows.append(rec)
         del z, g, el, er, zr, elr, err, out, lse, t
@@ -332,3 +383,20 @@ if args.v2:
               f"{m['v2_fwd'] / m['gat_fwd']:.2f} | {m['v2_fwd_bwd']:.2f} | "
               f"{r['v2_fwd_bwd_ratio']:.2f} | "
               f"{m['v2_fwd_bwd'] / m['gat_fwd_bwd']:.2f} |")
+
+if args.dot:
+    v2 = " / v2 |" if args.v2 else ""
+    print("\n| dtype | H | dot fwd kernel | dot bwd dst (CSR) | dot bwd src "
+          "(CSC) | dot fwd | / spmm |" + v2 + " dot f+b | / spmm |" + v2)
+    print("|---|---|---|---|---|---|---|---|---|" + ("---|---|" if args.v2
+                                                      else ""))
+    for r in rows:
+        m = r["ms"]
+        f_v2 = f" {m['dot_fwd'] / m['v2_fwd']:.2f} |" if args.v2 else ""
+        fb_v2 = (f" {m['dot_fwd_bwd'] / m['v2_fwd_bwd']:.2f} |"
+                 if args.v2 else "")
+        print(f"| {r['dtype']} | {r['H']} | {m['dot_fwd_k']:.2f} | "
+              f"{m['dot_bwd_dst']:.2f} | {m['dot_bwd_src']:.2f} | "
+              f"{m['dot_fwd']:.2f} | {r['dot_fwd_ratio']:.2f} |" + f_v2
+              + f" {m['dot_fwd_bwd']:.2f} | {r['dot_fwd_bwd_ratio']:.2f} |"
+              + fb_v2)
