@@ -113,20 +113,37 @@ static std::vector<torch::Tensor> scale_rows_live(torch::Tensor g,
 // GPU-only: ops.pack_rows_reference is the torch mirror of the layout
 static torch::Tensor pack_rows(torch::Tensor x) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 2, "pack_rows is the GPU path");
-  auto packed = torch::empty({x.size(0), packed_layout(x.size(1)).stride_words},
-                             x.options().dtype(torch::kInt));
-  pack_rows_hip(x, packed);
+  const bool bf16 = x.scalar_type() == torch::kBFloat16;
+  TORCH_CHECK(bf16 || x.scalar_type() == torch::kFloat,
+              "pack_rows: fp32 or bf16 [N, F] only");
+  auto packed = torch::empty(
+      {x.size(0), packed_layout(x.size(1), bf16 ? 2 : 4).stride_words},
+      x.options().dtype(torch::kInt));
+  if (bf16)
+    pack_rows_bf16_hip(x, packed);
+  else
+    pack_rows_hip(x, packed);
   return packed;
 }
 
+// bf16: packed holds bf16 records (pack_rows of a bf16 tensor) and the result
+// is bf16; vec is the bf16 gather's lane width (4, 8 or 0 for its own choice)
 static torch::Tensor spmm_packed(torch::Tensor indptr, torch::Tensor indices,
                                  torch::Tensor packed, int64_t F,
                                  torch::Tensor dst_scale,
-                                 torch::Tensor row_order, int64_t num_rows) {
+                                 torch::Tensor row_order, int64_t num_rows,
+                                 bool bf16, int64_t vec) {
   TORCH_CHECK(packed.is_cuda(), "spmm_packed is the GPU path");
-  auto out = torch::empty({num_rows, F},
-                          packed.options().dtype(torch::kFloat));
-  spmm_packed_hip(indptr, indices, packed, F, dst_scale, row_order, out);
+  TORCH_CHECK(bf16 || vec == 0,
+              "spmm_packed: vec selects the bf16 lane width only");
+  auto out = torch::empty(
+      {num_rows, F},
+      packed.options().dtype(bf16 ? torch::kBFloat16 : torch::kFloat));
+  if (bf16)
+    spmm_packed_bf16_hip(indptr, indices, packed, F, dst_scale, row_order,
+                         out, vec);
+  else
+    spmm_packed_hip(indptr, indices, packed, F, dst_scale, row_order, out);
   return out;
 }
 
@@ -269,9 +286,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("scale_rows_live", &scale_rows_live,
         "g * inv per row -> (scaled, n_live = 1 + last non-zero row, int32)");
   m.def("pack_rows", &pack_rows,
-        "fp32 [N, F] -> packed rows int32 [N, stride_words]");
+        "fp32 or bf16 [N, F] -> packed rows int32 [N, stride_words]");
   m.def("spmm_packed", &spmm_packed,
-        "CSR SpMM over packed rows (fp32, dst_scale epilogue)");
+        "CSR SpMM over packed rows (fp32 or bf16, dst_scale epilogue)",
+        py::arg("indptr"), py::arg("indices"), py::arg("packed"),
+        py::arg("F"), py::arg("dst_scale"), py::arg("row_order"),
+        py::arg("num_rows"), py::arg("bf16") = false, py::arg("vec") = 0);
   m.def("gather_rows", &gather_rows, "out[i,:] = src[idx[i],:]");
   m.def("gather_rows_out", &gather_rows_out,
         "gather into a preallocated out buffer");

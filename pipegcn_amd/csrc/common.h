@@ -134,12 +134,19 @@ void spmm_drop_hip(torch::Tensor indptr, torch::Tensor indices,
 // uint32 exclusive prefix count} (one per 32 columns), padding up to hdr_words
 // (a multiple of 4), then the row's non-zero values in column order. Row u
 // starts at word u * stride_words (a multiple of 32).
+//
+// elem_size 2 (csrc/hip/spmm_packed_bf16.hip) is the record of a bf16 row:
+// mask_words counts header entries of 3 words {uint32 mask_lo, uint32
+// mask_hi, uint32 exclusive prefix count}, one per 64 columns; after the
+// padding to hdr_words come the non-zero values, 2 bytes each, then at least
+// 3 words of slack (a lane loads the 3 aligned words from word rank / 2 on,
+// rank <= F). The fp32 layout is elem_size 4, the default.
 struct PackedLayout {
   int64_t mask_words;
   int64_t hdr_words;
   int64_t stride_words;
 };
-PackedLayout packed_layout(int64_t F);
+PackedLayout packed_layout(int64_t F, int64_t elem_size = 4);
 // packed: int32 [N, stride_words], written for every row of x (fp32 [N, F]);
 // padding and the value slots past a row's non-zero count stay unwritten.
 void pack_rows_hip(torch::Tensor x, torch::Tensor packed);
@@ -149,6 +156,15 @@ void pack_rows_hip(torch::Tensor x, torch::Tensor packed);
 void spmm_packed_hip(torch::Tensor indptr, torch::Tensor indices,
                      torch::Tensor packed, int64_t F, torch::Tensor dst_scale,
                      torch::Tensor row_order, torch::Tensor out);
+// The same pair for bf16 (csrc/hip/spmm_packed_bf16.hip): x bf16 [N, F] ->
+// packed int32 [N, packed_layout(F, 2).stride_words]; out bf16 [num_rows, F],
+// bitwise the dense bf16 kernel's (fp32 accumulation, one rounding). vec is
+// the lane width, 4 or 8 columns, 0 to choose by F.
+void pack_rows_bf16_hip(torch::Tensor x, torch::Tensor packed);
+void spmm_packed_bf16_hip(torch::Tensor indptr, torch::Tensor indices,
+                          torch::Tensor packed, int64_t F,
+                          torch::Tensor dst_scale, torch::Tensor row_order,
+                          torch::Tensor out, int64_t vec = 0);
 
 // out[i,:] = src[idx[i],:]
 void gather_rows_hip(torch::Tensor src, torch::Tensor idx, torch::Tensor out);

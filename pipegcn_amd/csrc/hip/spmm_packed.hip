@@ -347,8 +347,19 @@ __global__ void spmm_packed_kernel(const int64_t* __restrict__ indptr,
 
 }  // namespace
 
-PackedLayout packed_layout(int64_t F) {
+PackedLayout packed_layout(int64_t F, int64_t elem_size) {
+  TORCH_CHECK(elem_size == 4 || elem_size == 2,
+              "packed_layout: fp32 or bf16 rows only");
   PackedLayout l;
+  if (elem_size == 2) {
+    // spmm_packed_bf16.hip: 3-word entries per 64 columns, 2-byte values
+    l.mask_words = (F + 63) / 64;
+    l.hdr_words = (3 * l.mask_words + 3) / 4 * 4;
+    // F slots rounded up to a word, then 3 slack words: a 3-word load may
+    // start at word nnz / 2 <= F / 2
+    l.stride_words = (l.hdr_words + (F + 1) / 2 + 3 + 31) / 32 * 32;
+    return l;
+  }
   l.mask_words = (F + 31) / 32;
   // header padded so the values start 16-byte aligned
   l.hdr_words = (2 * l.mask_words + 3) / 4 * 4;

@@ -145,85 +145,145 @@ def scale_rows_live(g: torch.Tensor, inv: torch.Tensor):
     return native().scale_rows_live(g, inv)
 
 
-def packed_row_layout(F: int):
+def _packed_elem_size(dtype, op: str) -> int:
+    if dtype == torch.float32:
+        return 4
+    if dtype == torch.bfloat16:
+        return 2
+    raise ValueError(f"{op}: fp32 or bf16 only, not {dtype}")
+
+
+def packed_row_layout(F: int, dtype=torch.float32):
     """(mask_words, hdr_words, stride_words) of a packed row of width F, in
-    4-byte words, as csrc/hip/spmm_packed.hip lays it out (docs/DESIGN.md,
-    "Packed rows"): mask_words header entries {uint32 mask, uint32 exclusive
-    prefix count}, one per 32 columns; padding to hdr_words (a multiple of
-    4, so the values start 16-byte aligned); then the non-zero values in
-    column order. stride_words leaves 8 words of slack after F value slots
-    and is a multiple of 32 (128 B)."""
+    4-byte words (docs/DESIGN.md, "Packed rows").
+
+    fp32 (csrc/hip/spmm_packed.hip): mask_words header entries {uint32 mask,
+    uint32 exclusive prefix count}, one per 32 columns; padding to hdr_words
+    (a multiple of 4, so the values start 16-byte aligned); then the non-zero
+    values in column order. stride_words leaves 8 words of slack after F
+    value slots and is a multiple of 32 (128 B).
+
+    bf16 (csrc/hip/spmm_packed_bf16.hip): mask_words header entries {uint32
+    mask_lo, uint32 mask_hi, uint32 exclusive prefix count}, one per 64
+    columns; padding to hdr_words (a multiple of 4); then the non-zero values,
+    2 bytes each, in column order. stride_words leaves 3 words of slack after
+    the word of the F-th slot and is a multiple of 32."""
+    if _packed_elem_size(dtype, "packed_row_layout") == 2:
+        mask_words = (F + 63) // 64
+        hdr_words = (3 * mask_words + 3) // 4 * 4
+        stride_words = (hdr_words + (F + 1) // 2 + 3 + 31) // 32 * 32
+        return mask_words, hdr_words, stride_words
     mask_words = (F + 31) // 32
     hdr_words = (2 * mask_words + 3) // 4 * 4
     stride_words = (hdr_words + F + 8 + 31) // 32 * 32
     return mask_words, hdr_words, stride_words
 
 
+def _i32(v: torch.Tensor) -> torch.Tensor:
+    # values >= 2^31 wrap to the int32 with the same bits
+    return ((v + 2 ** 31) % 2 ** 32 - 2 ** 31).int()
+
+
 def pack_rows_reference(x: torch.Tensor) -> torch.Tensor:
-    """The torch mirror of the device row-packing kernel: fp32 [N, F] ->
-    int32 [N, stride_words]. Runs on x's device (CPU-capable). Header and
-    the leading nnz value slots of each row are what the kernel writes, bit
-    for bit; everything else (which the kernel leaves unwritten) is 0 here.
-    "Non-zero" is v != 0: both zeros are dropped, NaN and +-Inf are kept."""
-    if x.dim() != 2 or x.dtype != torch.float32:
-        raise ValueError("pack_rows_reference: fp32 [N, F] only")
+    """The torch mirror of the device row-packing kernels: fp32 or bf16
+    [N, F] -> int32 [N, stride_words]. Runs on x's device (CPU-capable).
+    Header and the leading nnz value slots of each row are what the kernel
+    writes, bit for bit; everything else (which the kernel leaves unwritten)
+    is 0 here. "Non-zero" is v != 0: both zeros are dropped, NaN and +-Inf
+    are kept."""
+    if x.dim() != 2 or x.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("pack_rows_reference: fp32 or bf16 [N, F] only")
     N, F = x.shape
-    W, hdr, stride = packed_row_layout(F)
+    W, hdr, stride = packed_row_layout(F, x.dtype)
+    bf16 = x.dtype == torch.bfloat16
     nz = x != 0
-    nzp = torch.zeros(N, W * 32, dtype=torch.int64, device=x.device)
+    nzp = torch.zeros(N, W * (64 if bf16 else 32), dtype=torch.int64,
+                      device=x.device)
     nzp[:, :F] = nz
-    nzp = nzp.view(N, W, 32)
-    mask = (nzp << torch.arange(32, device=x.device)).sum(-1)
-    cnt = nzp.sum(-1)
+    # 32-bit mask words, and the non-zeros per header entry
+    words = nzp.view(N, -1, 32)
+    mask = (words << torch.arange(32, device=x.device)).sum(-1)
+    cnt = nzp.view(N, W, -1).sum(-1)
     prefix = cnt.cumsum(-1) - cnt
     out = torch.zeros(N, stride, dtype=torch.int32, device=x.device)
-    # values >= 2^31 wrap to the int32 with the same bits
-    out[:, 0:2 * W:2] = ((mask + 2 ** 31) % 2 ** 32 - 2 ** 31).int()
-    out[:, 1:2 * W:2] = prefix.int()
     rank = nz.long().cumsum(-1) - 1
     rows = torch.arange(N, device=x.device).unsqueeze(1).expand(N, F)
+    if bf16:
+        out[:, 0:3 * W:3] = _i32(mask[:, 0::2])
+        out[:, 1:3 * W:3] = _i32(mask[:, 1::2])
+        out[:, 2:3 * W:3] = prefix.int()
+        # 2-byte slots, the even one in the low half of its word
+        out.view(torch.int16)[rows[nz], 2 * hdr + rank[nz]] = \
+            x.contiguous().view(torch.int16)[nz]
+        return out
+    out[:, 0:2 * W:2] = _i32(mask)
+    out[:, 1:2 * W:2] = prefix.int()
     out[rows[nz], hdr + rank[nz]] = x.contiguous().view(torch.int32)[nz]
     return out
 
 
-def unpack_rows_reference(packed: torch.Tensor, F: int) -> torch.Tensor:
+def unpack_rows_reference(packed: torch.Tensor, F: int,
+                          dtype=torch.float32) -> torch.Tensor:
     """Inverse of the packing (dropped entries come back as +0.0): int32
-    [N, stride_words] -> fp32 [N, F]. Reads only the header and the value
-    slots the header points at."""
-    W, hdr, stride = packed_row_layout(F)
+    [N, stride_words] of the layout of `dtype` -> [N, F] of that dtype.
+    Reads only the header and the value slots the header points at."""
+    W, hdr, stride = packed_row_layout(F, dtype)
     if packed.dim() != 2 or packed.shape[1] != stride \
             or packed.dtype != torch.int32:
         raise ValueError("unpack_rows_reference: not packed rows of width "
                          f"{F}")
     N = packed.shape[0]
-    mask = packed[:, 0:2 * W:2].long() & _M32
-    prefix = packed[:, 1:2 * W:2].long()
+    bf16 = dtype == torch.bfloat16
+    if bf16:
+        mask = torch.stack((packed[:, 0:3 * W:3], packed[:, 1:3 * W:3]),
+                           -1).long() & _M32       # [N, W, 2]
+        prefix = packed[:, 2:3 * W:3].long()
+        vals = packed.contiguous().view(torch.int16)[:, 2 * hdr:]
+    else:
+        mask = (packed[:, 0:2 * W:2].long() & _M32).unsqueeze(-1)
+        prefix = packed[:, 1:2 * W:2].long()
+        vals = packed[:, hdr:]
     bits = (mask.unsqueeze(-1) >> torch.arange(32, device=packed.device)) & 1
+    bits = bits.reshape(N, W, -1)                   # the entry's columns
     rank = prefix.unsqueeze(-1) + bits.cumsum(-1) - bits
-    nz = bits.view(N, W * 32)[:, :F].bool()
-    rank = rank.view(N, W * 32)[:, :F]
-    vals = packed[:, hdr:].gather(1, rank.clamp(max=stride - hdr - 1))
-    return torch.where(nz, vals, torch.zeros_like(vals)).view(torch.float32)
+    nz = bits.reshape(N, -1)[:, :F].bool()
+    rank = rank.reshape(N, -1)[:, :F]
+    vals = vals.gather(1, rank.clamp(max=vals.shape[1] - 1))
+    return torch.where(nz, vals, torch.zeros_like(vals)).view(dtype)
 
 
 def pack_rows(x: torch.Tensor) -> torch.Tensor:
-    """Packed rows of a fp32 [N, F] tensor (device kernel on the GPU, the
-    torch mirror elsewhere)."""
+    """Packed rows of a fp32 or bf16 [N, F] tensor (device kernel on the
+    GPU, the torch mirror elsewhere)."""
+    if x.dim() != 2 or x.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("pack_rows: fp32 or bf16 [N, F] only")
     if x.is_cuda:
         return native().pack_rows(x.contiguous())
     return pack_rows_reference(x)
 
 
-def _spmm_packed_width(F: int) -> bool:
-    """Static routing of the forward SpMM by feature width, read off the
-    `spmm_bench --density` table on the Reddit shape (profiles/README.md,
-    "Packed-row forward SpMM"). Pack pass plus packed gather against the
-    dense kernel, at the one half / one quarter of non-zeros that dropout
-    and dropout after ReLU leave: F=602 27.0 / 20.4 vs 41.3 ms, F=256 9.7 /
-    6.8 vs 15.5, F=128 6.5 / 6.3 vs 9.9, F=64 5.4 / 5.3 vs 7.2. It wins at
-    every measured width, layer 0 included; narrower ones were not measured
-    and stay dense. With nothing to skip it costs 7-13 % (F=602 / F=256)
-    and saves 3-6 % at F=128 / F=64."""
+def _spmm_packed_width(F: int, dtype=torch.float32) -> bool:
+    """Static routing of the forward SpMM by feature width and dtype, read
+    off the `spmm_bench --density` tables on the Reddit shape
+    (profiles/README.md, "Packed-row forward SpMM" and "Packed-row forward
+    SpMM, bf16"). Pack pass plus packed gather against the dense kernel, at
+    the one half / one quarter of non-zeros that dropout and dropout after
+    ReLU leave.
+
+    fp32: F=602 27.0 / 20.4 vs 41.3 ms, F=256 9.7 / 6.8 vs 15.5, F=128 6.5 /
+    6.3 vs 9.9, F=64 5.4 / 5.3 vs 7.2. It wins at every measured width,
+    layer 0 included; narrower ones were not measured and stay dense. With
+    nothing to skip it costs 7-13 % (F=602 / F=256) and saves 3-6 % at
+    F=128 / F=64.
+
+    bf16: F=602 19.0 / 18.7 vs 21.5 ms, F=256 7.2 / 6.9 vs 8.5: packed from
+    256 columns on, by 11-19 % against a spread between rounds of at most
+    2 %. F=128 6.6 / 6.4 vs 5.4 and F=64 6.5 / 6.4 vs 4.8 lose (the bf16
+    gather costs about 6.4 ms per chunk whatever the row holds) and stay
+    dense, as do the unmeasured widths below 256. With nothing to skip it
+    costs 13-22 % at F=256 / F=602."""
+    if dtype == torch.bfloat16:
+        return F >= 256
     return F >= 64
 
 
@@ -231,21 +291,22 @@ def _spmm_packed_route(feat: torch.Tensor) -> bool:
     """Whether _SpmmMean.forward takes the packed path for this input.
     PIPEGCN_SPMM_PACKED=0 pins the dense kernel everywhere. No density is
     counted here: that would need a device sync."""
-    if (not feat.is_cuda or feat.dtype != torch.float32
+    if (not feat.is_cuda
+            or feat.dtype not in (torch.float32, torch.bfloat16)
             or os.environ.get("PIPEGCN_SPMM_PACKED", "1") == "0"
-            or not _spmm_packed_width(feat.shape[1])):
+            or not _spmm_packed_width(feat.shape[1], feat.dtype)):
         return False
     # the transient packed buffer: near the memory ceiling (papers100M
     # sizing) stay dense, as the row-order autotune stays put there
     free, _ = torch.cuda.mem_get_info(feat.device)
-    need = feat.shape[0] * packed_row_layout(feat.shape[1])[2] * 4
+    need = feat.shape[0] * packed_row_layout(feat.shape[1], feat.dtype)[2] * 4
     return free >= need + (2 << 30)
 
 
 def spmm_packed(csr: CSR, feat: torch.Tensor,
                 scale: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """`spmm(csr, feat, scale)` for fp32 GPU inputs, skipping feat's zeros:
-    feat is packed row by row (header of non-zero bits + the non-zero
+    """`spmm(csr, feat, scale)` for fp32 or bf16 GPU inputs, skipping feat's
+    zeros: feat is packed row by row (header of non-zero bits + the non-zero
     values), then gathered packed. Bitwise equal to `spmm` on any input;
     faster when a large share of feat is exactly zero (after dropout and
     ReLU). The packed buffer is transient."""
@@ -254,8 +315,9 @@ def spmm_packed(csr: CSR, feat: torch.Tensor,
             f"spmm_packed: feat has {feat.shape[0]} rows but the graph "
             f"references {csr.num_cols} source nodes (an under-sized feat "
             "would be an out-of-bounds GPU gather)")
-    if not feat.is_cuda or feat.dtype != torch.float32 or feat.dim() != 2:
-        raise ValueError("spmm_packed: fp32 [N, F] GPU tensors only")
+    if (not feat.is_cuda or feat.dim() != 2
+            or feat.dtype not in (torch.float32, torch.bfloat16)):
+        raise ValueError("spmm_packed: fp32 or bf16 [N, F] GPU tensors only")
     s = scale if scale is not None else torch.Tensor()
     # the dense path's row order: its cached autotune decision for this
     # (graph, F) if it made one, else the LPT order (no second autotune)
@@ -264,7 +326,8 @@ def spmm_packed(csr: CSR, feat: torch.Tensor,
         ro = torch.Tensor()
     packed = native().pack_rows(feat.contiguous())
     return native().spmm_packed(csr.indptr, csr.indices, packed,
-                                feat.shape[1], s, ro, csr.num_rows)
+                                feat.shape[1], s, ro, csr.num_rows,
+                                feat.dtype == torch.bfloat16)
 
 
 def _spmm_mean_forward(graph: HaloGraph, feat: torch.Tensor,

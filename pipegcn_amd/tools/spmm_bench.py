@@ -34,6 +34,8 @@ Usage (on a GPU box):
     python -m pipegcn_amd.tools.spmm_bench --f 256 --edge-drop 0.2 0.5 0.8
     python -m pipegcn_amd.tools.spmm_bench [--f 602 256] [--rounds 5]
     python -m pipegcn_amd.tools.spmm_bench --f 256 --density 0.25 0.5 1.0
+    python -m pipegcn_amd.tools.spmm_bench --dtype bf16 --density 0.25 0.5 \
+        --packed-vec 4 8
     python -m pipegcn_amd.tools.spmm_bench --f 256 --dead-frac 0 0.34 0.92
     python -m pipegcn_amd.tools.spmm_bench --max
 """
@@ -54,61 +56,71 @@ def build(n=232_965, avg_deg=492, seed=0):
     return HaloGraph.from_edges(u, v, n, n).to("cuda"), int(v.numel())
 
 
-def density_table(hg, E, inv, widths, densities, rounds, iters):
+def density_table(hg, E, inv, widths, densities, rounds, iters,
+                  dtype=torch.float32, vecs=(0,)):
     """Dense SpMM, pack pass and packed SpMM on features with the share
     `density` of non-zeros, alternating in the same rounds. Prints best ms
-    and physical bytes per edge (dense: the row; packed: header plus the
-    mean non-zero payload), and checks the two outputs bitwise."""
+    with the spread between rounds (worst / best - 1, the largest of the
+    three) and physical bytes per edge (dense: the row; packed: header plus
+    the mean non-zero payload), and checks the two outputs bitwise. `vecs`
+    are the lane widths of the bf16 packed gather to time (0: its own
+    choice), one line each."""
     from pipegcn_amd import native, ops
 
     n = hg.num_all
     csr = hg.csr
     ro = csr.row_order
     s = inv
-    print("    F  density |  dense ms  B/edge |  pack ms | packed ms  B/edge"
-          " | packed+pack vs dense")
-    for F in widths:
-        W, _, stride = ops.packed_row_layout(F)
-        for d in densities:
-            g = torch.Generator(device="cuda").manual_seed(F)
-            feat = torch.randn(n, F, device="cuda", generator=g)
-            feat *= torch.rand(n, F, device="cuda", generator=g) < d
-            packed = native().pack_rows(feat)
-            nnz = int((feat != 0).sum())
+    bf16 = dtype == torch.bfloat16
+    es, bits = (2, torch.int16) if bf16 else (4, torch.int32)
+    print("    F  density vec |  dense ms  B/edge |  pack ms | packed ms  "
+          "B/edge | packed+pack vs dense | spread")
+    for F, d, vec in ((F, d, vec) for F in widths for d in densities
+                      for vec in vecs):
+        W, _, stride = ops.packed_row_layout(F, dtype)
+        g = torch.Generator(device="cuda").manual_seed(F)
+        feat = torch.randn(n, F, device="cuda", generator=g)
+        feat *= torch.rand(n, F, device="cuda", generator=g) < d
+        feat = feat.to(dtype)
+        packed = native().pack_rows(feat)
+        nnz = int((feat != 0).sum())
 
-            def dense():
-                return native().spmm(csr.indptr, csr.indices, feat, s,
-                                     torch.Tensor(), ro, csr.num_rows)
+        def dense():
+            return native().spmm(csr.indptr, csr.indices, feat, s,
+                                 torch.Tensor(), ro, csr.num_rows)
 
-            def pack():
-                return native().pack_rows(feat)
+        def pack():
+            return native().pack_rows(feat)
 
-            def gather():
-                return native().spmm_packed(csr.indptr, csr.indices, packed,
-                                            F, s, ro, csr.num_rows)
+        def gather():
+            return native().spmm_packed(csr.indptr, csr.indices, packed,
+                                        F, s, ro, csr.num_rows, bf16, vec)
 
-            assert torch.equal(dense().view(torch.int32),
-                               gather().view(torch.int32)), \
-                f"F={F} density={d}: packed SpMM differs from dense"
-            best = {}
-            for _ in range(rounds):
-                for name, fn in (("dense", dense), ("pack", pack),
-                                 ("packed", gather)):
+        assert torch.equal(dense().view(bits), gather().view(bits)), \
+            f"F={F} density={d}: packed SpMM differs from dense"
+        best, worst = {}, {}
+        for _ in range(rounds):
+            for name, fn in (("dense", dense), ("pack", pack),
+                             ("packed", gather)):
+                fn()
+                torch.cuda.synchronize()
+                t0 = time.time()
+                for _ in range(iters):
                     fn()
-                    torch.cuda.synchronize()
-                    t0 = time.time()
-                    for _ in range(iters):
-                        fn()
-                    torch.cuda.synchronize()
-                    t = (time.time() - t0) / iters * 1e3
-                    best[name] = min(best.get(name, t), t)
-            b_dense = 4 * F
-            b_packed = 8 * W + 4 * nnz / n
-            print(f"{F:5d}  {d:7.2f} | {best['dense']:9.2f}  {b_dense:6d} |"
-                  f" {best['pack']:8.3f} | {best['packed']:9.2f} "
-                  f"{b_packed:7.0f} | "
-                  f"{(best['packed'] + best['pack']) / best['dense']:.3f}x")
-            del feat, packed
+                torch.cuda.synchronize()
+                t = (time.time() - t0) / iters * 1e3
+                best[name] = min(best.get(name, t), t)
+                worst[name] = max(worst.get(name, t), t)
+        b_dense = es * F
+        b_packed = (12 if bf16 else 8) * W + es * nnz / n
+        spread = max(worst[k] / best[k] - 1 for k in best)
+        print(f"{F:5d}  {d:7.2f} {vec:3d} | {best['dense']:9.2f}  "
+              f"{b_dense:6d} |"
+              f" {best['pack']:8.3f} | {best['packed']:9.2f} "
+              f"{b_packed:7.0f} | "
+              f"{(best['packed'] + best['pack']) / best['dense']:.3f}x"
+              f" | {100 * spread:.1f}%", flush=True)
+        del feat, packed
 
 
 def dead_rows_table(hg, inv, widths, fracs, dtype, rounds, iters):
@@ -404,7 +416,11 @@ def main():
                     help="instead of the lane-width A/B: for each F and "
                          "each share D of non-zero features, time the "
                          "dense SpMM, the pack pass and the packed SpMM "
-                         "(fp32)")
+                         "(--dtype as given)")
+    ap.add_argument("--packed-vec", type=int, nargs="+", default=[0],
+                    choices=[0, 4, 8], metavar="V",
+                    help="with --density --dtype bf16: the lane widths of "
+                         "the packed gather to time (0: its own choice)")
     ap.add_argument("--dead-frac", type=float, nargs="+", default=None,
                     metavar="S",
                     help="instead of the lane-width A/B: for each F and "
@@ -451,10 +467,11 @@ def main():
                         else torch.float32, args.rounds, args.iters)
         return
     if args.density:
-        if args.dtype != "fp32":
-            raise SystemExit("--density: the packed path is fp32 only")
+        if args.dtype == "fp32" and args.packed_vec != [0]:
+            raise SystemExit("--packed-vec: the bf16 gather's lane width")
         density_table(hg, E, inv, args.f, args.density, args.rounds,
-                      args.iters)
+                      args.iters, torch.bfloat16 if args.dtype == "bf16"
+                      else torch.float32, args.packed_vec)
         return
 
     if args.dead_frac:

@@ -23,6 +23,7 @@ ext = CUDAExtension(
         "pipegcn_amd/csrc/partitioner.cpp",
         "pipegcn_amd/csrc/hip/kernels.hip",
         "pipegcn_amd/csrc/hip/spmm_packed.hip",
+        "pipegcn_amd/csrc/hip/spmm_packed_bf16.hip",
         "pipegcn_amd/csrc/hip/spmm_max.hip",
         "pipegcn_amd/csrc/hip/spmm_drop.hip",
         "pipegcn_amd/csrc/hip/dual_gemm.hip",
