@@ -92,16 +92,28 @@ def density_table(hg, E, inv, widths, densities, rounds, iters,
         def pack():
             return native().pack_rows(feat)
 
-        def gather():
+        def gather(lds="0"):
+            # fp32: the register-fed gather ("0") or the LDS-staged one
+            os.environ["PIPEGCN_SPMM_PACKED_LDS"] = lds
             return native().spmm_packed(csr.indptr, csr.indices, packed,
                                         F, s, ro, csr.num_rows, bf16, vec)
 
-        assert torch.equal(dense().view(bits), gather().view(bits)), \
+        def staged():
+            return gather("1")
+
+        fns = [("dense", dense), ("pack", pack), ("packed", gather)]
+        ref = dense().view(bits)
+        assert torch.equal(ref, gather().view(bits)), \
             f"F={F} density={d}: packed SpMM differs from dense"
+        # the launcher stages three-chunk rows only
+        if not bf16 and (F + 255) // 256 == 3:
+            fns.append(("staged", staged))
+            assert torch.equal(ref, staged().view(bits)), \
+                f"F={F} density={d}: staged packed SpMM differs from dense"
+        del ref
         best, worst = {}, {}
         for _ in range(rounds):
-            for name, fn in (("dense", dense), ("pack", pack),
-                             ("packed", gather)):
+            for name, fn in fns:
                 fn()
                 torch.cuda.synchronize()
                 t0 = time.time()
@@ -119,7 +131,12 @@ def density_table(hg, E, inv, widths, densities, rounds, iters,
               f" {best['pack']:8.3f} | {best['packed']:9.2f} "
               f"{b_packed:7.0f} | "
               f"{(best['packed'] + best['pack']) / best['dense']:.3f}x"
-              f" | {100 * spread:.1f}%", flush=True)
+              f" | {100 * spread:.1f}%"
+              + (f" | staged {best['staged']:.2f} ms "
+                 f"(worst {worst['staged']:.2f}, packed worst "
+                 f"{worst['packed']:.2f})" if "staged" in best else ""),
+              flush=True)
+        os.environ.pop("PIPEGCN_SPMM_PACKED_LDS", None)
         del feat, packed
 
 
