@@ -49,6 +49,12 @@ def create_parser(argv=None):
                              "dropping an edge's attention coefficient, per "
                              "head, in training (--model gat, gatv2, "
                              "transformer)")
+    parser.add_argument("--beta-gate", "--beta_gate", action="store_true",
+                        help="gate the transformer layers as UniMP trains "
+                             "them (beta=True): a learned per-node sigmoid "
+                             "mixes the skip projection and the attention "
+                             "aggregate instead of adding them (--model "
+                             "transformer only)")
     parser.add_argument("--edge-drop", "--edge_drop", type=_edge_drop_rate,
                         default=0.0,
                         help="edge dropout (DropEdge) of the GraphSAGE-mean "

@@ -375,5 +375,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("num_cols"), py::arg("num_heads"), py::arg("scale"),
         py::arg("drop_key") = 0, py::arg("drop_thr") = 0,
         py::arg("drop_scale") = 1.0);
+  // GPU-only: ops.gated_residual composes the CPU path from torch ops
+  m.def("gate_fwd", &gate_fwd_hip,
+        "beta gate: sigmoid(<a, r> + <b, m>) mix of r and m -> (out, beta)",
+        py::arg("r"), py::arg("m"), py::arg("a"), py::arg("b"));
+  m.def("gate_bwd", &gate_bwd_hip,
+        "beta gate backward -> (d_r, d_m, da, db), da/db reproducible",
+        py::arg("g"), py::arg("r"), py::arg("m"), py::arg("a"), py::arg("b"),
+        py::arg("beta"));
   m.attr("with_hip") = true;
 }

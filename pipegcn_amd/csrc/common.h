@@ -303,6 +303,18 @@ torch::Tensor dot_bwd_src_hip(
     torch::Tensor row_order, int64_t num_cols, int64_t H, double scale,
     int64_t drop_key, int64_t drop_thr, double drop_scale);
 
+// Beta gate of the graph transformer layer (csrc/hip/gate.hip):
+//   beta_v = sigmoid(<a, r_v> + <b, m_v>), out_v = beta_v r_v + (1 - beta_v) m_v
+// r/m/g/out/d_r/d_m are fp32 or bf16 [N, F] of one dtype, a/b fp32 [F], beta
+// fp32 [N]; arithmetic in fp32. -> {out, beta}.
+std::vector<torch::Tensor> gate_fwd_hip(torch::Tensor r, torch::Tensor m,
+                                        torch::Tensor a, torch::Tensor b);
+// -> {d_r, d_m, da, db}; da/db are fp32 [F], summed in a fixed order without
+// atomics: bitwise reproducible for a given (N, F).
+std::vector<torch::Tensor> gate_bwd_hip(torch::Tensor g, torch::Tensor r,
+                                        torch::Tensor m, torch::Tensor a,
+                                        torch::Tensor b, torch::Tensor beta);
+
 // Fused dual GEMM for the GraphSAGE layer forward:
 //   out[M,N] = x1[M,K] @ w1[N,K]^T + x2[M,K] @ w2[N,K]^T + bias[N]
 // fp32, MFMA (v_mfma_f32_32x32x2_f32). Weights in torch Linear layout [N,K],

@@ -1144,6 +1144,70 @@ def dot_aggregate_csr(csr: CSR, q: torch.Tensor, kv: torch.Tensor,
                                 num_heads, scale)[0]
 
 
+def _gate_mix(r, m, a, b):
+    """The gate from the folded vectors, as plain torch ops: the CPU path,
+    and the formula the kernels are measured against."""
+    beta = torch.sigmoid(r @ a + m @ b).unsqueeze(1)
+    return beta * r + (1 - beta) * m
+
+
+class _GatedResidual(torch.autograd.Function):
+    """out = beta r + (1 - beta) m with beta = sigmoid(<a, r> + <b, m>) per
+    row, on the gfx950 kernels (csrc/hip/gate.hip): one pass forward, one
+    backward. Saves r, m and the [N] fp32 beta; da and db are summed in a
+    fixed order, so they are bitwise reproducible."""
+
+    @staticmethod
+    def forward(ctx, r, m, a, b):
+        out, beta = native().gate_fwd(r, m, a, b)
+        ctx.save_for_backward(r, m, a, b, beta)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        r, m, a, b, beta = ctx.saved_tensors
+        return tuple(native().gate_bwd(g.contiguous(), r, m, a, b, beta))
+
+
+def gated_residual(r: torch.Tensor, m: torch.Tensor,
+                   weight: torch.Tensor) -> torch.Tensor:
+    """UniMP's beta gate between the skip projection r and the attention
+    aggregate m, both [N, F]; weight is the [1, 3F] matrix of a bias-free
+    Linear over [r | m | r - m]:
+
+        beta = sigmoid([r | m | r - m] @ weight^T)       [N, 1]
+        out  = beta * r + (1 - beta) * m
+
+    The logit folds to <a, r> + <b, m> with a = w_r + w_d, b = w_m - w_d; the
+    fold is two [F] torch ops outside the node, so autograd turns the
+    kernels' da, db into the weight's gradient. On the GPU (fp32 or bf16
+    storage, fp32 arithmetic) no [N, F] temporary and no [N, 3F]
+    concatenation exists; CPU tensors run the same formula as torch ops."""
+    if r.dim() != 2 or m.shape != r.shape:
+        raise ValueError(f"gated_residual: r {tuple(r.shape)} and m "
+                         f"{tuple(m.shape)} must be equal [N, F] shapes")
+    if m.dtype != r.dtype or not r.is_floating_point():
+        raise ValueError(f"gated_residual: r {r.dtype} and m {m.dtype} must "
+                         "share one floating dtype")
+    feats = r.shape[1]
+    if tuple(weight.shape) != (1, 3 * feats):
+        raise ValueError(f"gated_residual: weight {tuple(weight.shape)} is "
+                         f"not [1, 3F] = [1, {3 * feats}]")
+    if not weight.is_floating_point() or weight.device != r.device \
+            or m.device != r.device:
+        raise ValueError("gated_residual: weight must be a floating tensor "
+                         "on the device of r and m")
+    if r.is_cuda and r.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"gated_residual: the GPU path is fp32 or bf16, "
+                         f"got {r.dtype}")
+    acc = torch.float64 if r.dtype == torch.float64 else torch.float32
+    w_r, w_m, w_d = weight.to(acc).view(3, feats)
+    a, b = w_r + w_d, w_m - w_d
+    if not r.is_cuda:
+        return _gate_mix(r.to(acc), m.to(acc), a, b).to(r.dtype)
+    return _GatedResidual.apply(r.contiguous(), m.contiguous(), a, b)
+
+
 class _BiasColsum(torch.autograd.Function):
     """x + b with the bias gradient through the native colsum (see
     sage_dual_linear: torch's own reduce is pathological for thin odd N)."""

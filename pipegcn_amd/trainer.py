@@ -183,6 +183,10 @@ def create_model(layer_size, args):
                 else f"--model {args.model}")
         raise NotImplementedError(
             f"--edge-drop does not combine with {what}")
+    beta_gate = getattr(args, "beta_gate", False)
+    if beta_gate and args.model != "transformer":
+        raise NotImplementedError(
+            "--beta-gate supports --model transformer only")
     if args.model == "graphsage":
         return GraphSAGE(layer_size, F.relu, args.use_pp, norm=args.norm,
                          dropout=args.dropout, n_linear=args.n_linear,
@@ -220,7 +224,8 @@ def create_model(layer_size, args):
                            dropout=args.dropout, n_linear=args.n_linear,
                            train_size=args.n_train,
                            n_heads=getattr(args, "n_heads", 1),
-                           attn_drop=getattr(args, "attn_drop", 0.0))
+                           attn_drop=getattr(args, "attn_drop", 0.0),
+                           beta=beta_gate)
     raise NotImplementedError(f"unknown model {args.model}")
 
 

@@ -44,6 +44,16 @@ spmm_max.hip) to the `--epoch` models, built and timed the same way.
 spmm_drop.hip) to the `--epoch` models, beside the same models without it.
 
     python tools/microbench/gat_bench.py --epoch --edge-drop 0.5
+
+`--gate` times the beta gate (csrc/hip/gate.hip). Alone it times
+ops.gated_residual on [num_in, F] rows, forward and forward+backward, against
+the eager composition (the CPU path's formula run on the device), reports
+min / median / max over the rounds and the achieved bytes/s against the
+model (forward 3 N F elements; backward 3 read + 2 written), and exits. With
+`--epoch` it adds the Transformer with 4 heads, without and with the gate.
+
+    python tools/microbench/gat_bench.py --gate [--rounds 7 --iters 20]
+    python tools/microbench/gat_bench.py --epoch --gate
 """
 import argparse
 import json
@@ -79,6 +89,9 @@ ap.add_argument("--pool", action="store_true",
 ap.add_argument("--edge-drop", "--edge_drop", type=float, default=0.0,
                 help="with --epoch: also time GraphSAGE-mean and GCN with "
                      "this edge dropout")
+ap.add_argument("--gate", action="store_true",
+                help="time the beta gate alone; with --epoch: the "
+                     "Transformer without and with it")
 args = ap.parse_args()
 if args.pool and not args.epoch:
     ap.error("--pool times whole epochs: use it with --epoch")
@@ -116,9 +129,9 @@ def timed(f):
     return (time.perf_counter() - t0) / args.iters * 1e3
 
 
-def bench(fns):
+def bench_rounds(fns):
     """fns: {name: callable}. Warm each, then alternate them round by
-    round; returns {name: median ms}."""
+    round; returns {name: [ms of each round]}."""
     for f in fns.values():
         f()
         f()
@@ -126,7 +139,51 @@ def bench(fns):
     for _ in range(args.rounds):
         for k, f in fns.items():
             samples[k].append(timed(f))
-    return {k: statistics.median(v) for k, v in samples.items()}
+    return samples
+
+
+def bench(fns):
+    """-> {name: median ms} of bench_rounds."""
+    return {k: statistics.median(v) for k, v in bench_rounds(fns).items()}
+
+
+def gate_bench():
+    N = rp.num_in
+    for dname in args.dtypes:
+        dtype = torch.bfloat16 if dname == "bf16" else torch.float32
+        es = 2 if dname == "bf16" else 4
+        gen = torch.Generator(device=dev).manual_seed(es)
+        r, m, g = (torch.randn(N, F, device=dev, generator=gen).to(dtype)
+                   for _ in range(3))
+        w = ((torch.rand(1, 3 * F, device=dev, generator=gen) * 2 - 1)
+             / (3 * F) ** 0.5)
+        rr, mr, wr = (t.clone().requires_grad_(True) for t in (r, m, w))
+
+        def eager(r, m, w):
+            w_r, w_m, w_d = w.view(3, F)
+            return ops._gate_mix(r.float(), m.float(), w_r + w_d,
+                                 w_m - w_d).to(dtype)
+
+        def fwd_bwd(f):
+            rr.grad = mr.grad = wr.grad = None
+            f(rr, mr, wr).backward(g)
+
+        samples = bench_rounds({
+            "fused_fwd": lambda: ops.gated_residual(r, m, w),
+            "eager_fwd": lambda: eager(r, m, w),
+            "fused_fwd_bwd": lambda: fwd_bwd(ops.gated_residual),
+            "eager_fwd_bwd": lambda: fwd_bwd(eager),
+        })
+        ms = {k: [round(x, 3) for x in (min(v), statistics.median(v), max(v))]
+              for k, v in samples.items()}
+        # the model: forward reads r, m and writes out; backward reads g, r,
+        # m and writes d_r, d_m
+        model = {"fused_fwd": 3 * N * F * es, "fused_fwd_bwd": 8 * N * F * es}
+        print(json.dumps(dict(
+            mode="gate", dtype=dname, N=N, F=F, ms_min_median_max=ms,
+            model_mb={k: round(b / 1e6, 1) for k, b in model.items()},
+            tb_per_s={k: round(b / ms[k][1] / 1e9, 3)
+                      for k, b in model.items()})), flush=True)
 
 
 def epoch_bench():
@@ -136,6 +193,7 @@ def epoch_bench():
     from pipegcn_amd.models.gatv2 import GATv2
     from pipegcn_amd.models.gcn import GCN
     from pipegcn_amd.models.sage import GraphSAGE
+    from pipegcn_amd.models.transformer import Transformer
     from pipegcn_amd.parallel import context as ctx
     from pipegcn_amd.trainer import (exchange_halo_values, get_layer_size)
 
@@ -166,6 +224,12 @@ def epoch_bench():
                            dict(use_pp=False, edge_drop=args.edge_drop), deg))
             models.append(("gcn-edge-drop", GCN,
                            dict(edge_drop=args.edge_drop), deg_all))
+        if args.gate:
+            for name, beta in (("transformer-4-heads", False),
+                               ("transformer-4-heads-gate", True)):
+                models.append((name, Transformer,
+                               dict(n_heads=4, attn_drop=args.attn_drop,
+                                    beta=beta), None))
         for name, cls, kw, d in models:
             torch.manual_seed(0)
             model = cls(layer_size, Fn.relu, dropout=0.5, norm="layer",
@@ -206,6 +270,10 @@ if args.epoch:
     dist.init_process_group("gloo", rank=0, world_size=1)
     epoch_bench()
     dist.destroy_process_group()
+    sys.exit(0)
+
+if args.gate:
+    gate_bench()
     sys.exit(0)
 
 # (key, thr, scale) of the native entry points; (0, 0, 1.0) is no dropout
