@@ -383,5 +383,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "beta gate backward -> (d_r, d_m, da, db), da/db reproducible",
         py::arg("g"), py::arg("r"), py::arg("m"), py::arg("a"), py::arg("b"),
         py::arg("beta"));
+  // GPU-only: the CPU keeps models.sync_bn.SyncBatchNorm.forward
+  m.def("bn_stats", &bn_stats_hip,
+        "column sums of x and x^2 in one read -> fp32 [2, F], reproducible",
+        py::arg("x"));
+  m.def("bn_apply", &bn_apply_hip,
+        "y = [relu]((x - mean) / std * w + b), mask taken in fp32",
+        py::arg("x"), py::arg("mean"), py::arg("std"), py::arg("w"),
+        py::arg("b"), py::arg("relu"));
+  m.def("bn_bwd_stats", &bn_bwd_stats_hip,
+        "batch-norm backward sums -> fp32 [2, F] (dbias, dweight)",
+        py::arg("dy"), py::arg("x"), py::arg("mean"), py::arg("std"),
+        py::arg("w"), py::arg("b"), py::arg("relu"));
+  m.def("bn_bwd_apply", &bn_bwd_apply_hip,
+        "dx = (w / n) / std * (n g' - dbias - x_hat dweight)", py::arg("dy"),
+        py::arg("x"), py::arg("mean"), py::arg("std"), py::arg("w"),
+        py::arg("b"), py::arg("dsum"), py::arg("whole_size"),
+        py::arg("relu"));
   m.attr("with_hip") = true;
 }

@@ -303,6 +303,31 @@ torch::Tensor dot_bwd_src_hip(
     torch::Tensor row_order, int64_t num_cols, int64_t H, double scale,
     int64_t drop_key, int64_t drop_thr, double drop_scale);
 
+// Fused SyncBatchNorm [+ReLU] (csrc/hip/batch_norm.hip). x/dy/y/dx are fp32
+// or bf16 contiguous [N, F] of one dtype, F >= 1, N >= 0; mean/std/w/b are
+// fp32 [F]; arithmetic and statistics in fp32. The column sums are added in
+// a fixed order without atomics: bitwise reproducible for a given (N, F).
+// -> fp32 [2, F]: sum_r x[r,:], then sum_r x[r,:]^2 (zeros when N == 0)
+torch::Tensor bn_stats_hip(torch::Tensor x);
+// -> y = (x - mean) / std * w + b, then max(., 0) if relu (decided on the
+// fp32 value before rounding); also the eval pass, with the running statistics
+torch::Tensor bn_apply_hip(torch::Tensor x, torch::Tensor mean,
+                           torch::Tensor std, torch::Tensor w,
+                           torch::Tensor b, bool relu);
+// x_hat and the ReLU mask are recomputed as the forward computed them; g' is
+// dy where the mask holds, else 0. -> fp32 [2, F]: dbias = sum g', then
+// dweight = sum g' x_hat
+torch::Tensor bn_bwd_stats_hip(torch::Tensor dy, torch::Tensor x,
+                               torch::Tensor mean, torch::Tensor std,
+                               torch::Tensor w, torch::Tensor b, bool relu);
+// dsum: fp32 [2, F] = (dbias, dweight) over all ranks, n = whole_size.
+// -> dx = (w / n) / std * (n g' - dbias - x_hat dweight)
+torch::Tensor bn_bwd_apply_hip(torch::Tensor dy, torch::Tensor x,
+                               torch::Tensor mean, torch::Tensor std,
+                               torch::Tensor w, torch::Tensor b,
+                               torch::Tensor dsum, double whole_size,
+                               bool relu);
+
 // Beta gate of the graph transformer layer (csrc/hip/gate.hip):
 //   beta_v = sigmoid(<a, r_v> + <b, m_v>), out_v = beta_v r_v + (1 - beta_v) m_v
 // r/m/g/out/d_r/d_m are fp32 or bf16 [N, F] of one dtype, a/b fp32 [F], beta

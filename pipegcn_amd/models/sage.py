@@ -231,11 +231,18 @@ class GNNBase(nn.Module):
         return self.dropout(h)
 
     def _norm_act(self, i, h):
-        """Inter-layer norm + activation: fused LayerNorm+ReLU on GPU."""
+        """Inter-layer norm + activation: fused LayerNorm+ReLU and fused
+        SyncBatchNorm+ReLU on GPU (PIPEGCN_BN_FUSED=0 keeps the batch norm's
+        separate torch ops)."""
+        fuse_relu = self.activation is torch.nn.functional.relu
         if h.is_cuda and self.use_norm and isinstance(self.norm[i],
                                                       nn.LayerNorm):
-            fuse_relu = self.activation is torch.nn.functional.relu
             h = ops.layer_norm_relu(h, self.norm[i], relu=fuse_relu)
+            return h if fuse_relu else self.activation(h)
+        if (h.is_cuda and self.use_norm
+                and isinstance(self.norm[i], SyncBatchNorm)
+                and os.environ.get("PIPEGCN_BN_FUSED", "1") != "0"):
+            h = ops.sync_batch_norm_relu(h, self.norm[i], relu=fuse_relu)
             return h if fuse_relu else self.activation(h)
         if self.use_norm:
             h = self.norm[i](h)

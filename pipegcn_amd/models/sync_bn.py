@@ -3,9 +3,17 @@
 Forward all-reduces sum(x) and sum(x^2) ([F] vectors) and normalizes by the
 GLOBAL train-node count `whole_size`; backward all-reduces dbias/dweight and
 computes dx = (w/n)/std * (n*g - dbias - x_hat*dweight). Collectives run on
-the main-thread process group (RCCL on GPU, gloo on CPU); the column
-reductions themselves are [N,F]->[F] torch ops (rocBLAS/eager — profiled as
-negligible next to SpMM).
+the main-thread process group (RCCL on GPU, gloo on CPU).
+
+On the GPU the models do not run this module's forward: GNNBase._norm_act
+hands the module to ops.sync_batch_norm_relu, which computes the same algebra
+with four fused kernels (csrc/hip/batch_norm.hip; docs/DESIGN.md, "Batch
+norm") and reads weight, bias, whole_size, eps, momentum and the running
+statistics from here. The code below is the CPU path, the path under
+PIPEGCN_BN_FUSED=0, and the composition the kernels are tested against: its
+[N,F] steps are separate torch ops, which cost 11.9 ms of a 79.7 ms yelp
+epoch at fp32 and 15.2 of 50.3 ms at bf16 (profiles/README.md, "Batch
+norm").
 
 Divergences from the reference implementation (the forward/backward algebra
 itself must match numerically for parity, and is textbook sync-BN):

@@ -1495,6 +1495,70 @@ def layer_norm_relu(x: torch.Tensor, ln: torch.nn.LayerNorm,
                                 ln.eps, relu)
 
 
+def _all_reduce_sum(t: torch.Tensor) -> None:
+    if torch.distributed.is_initialized() \
+            and torch.distributed.get_world_size() > 1:
+        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.SUM)
+
+
+class _SyncBatchNormReLU(torch.autograd.Function):
+    """Training-mode SyncBatchNorm [+ReLU] on the gfx950 kernels
+    (csrc/hip/batch_norm.hip): bn_stats, one all-reduce of the [2, F] sums,
+    the [F] algebra of models.sync_bn as torch ops, bn_apply. Saves x in its
+    own dtype and four [F] vectors: x_hat and the ReLU mask are recomputed in
+    the backward (bn_bwd_stats, one all-reduce of (dbias, dweight),
+    bn_bwd_apply). mean and var count as constants in the backward, as in
+    SyncBatchNormFunc."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, bn, relu):
+        x, w, b = x.contiguous(), w.contiguous(), b.contiguous()
+        sums = native().bn_stats(x)
+        _all_reduce_sum(sums)
+        n = bn.whole_size
+        mean = sums[0] / n
+        var = (sums[1] - mean * sums[0]) / n
+        bn.running_mean.mul_(1 - bn.momentum).add_(mean * bn.momentum)
+        bn.running_var.mul_(1 - bn.momentum).add_(var * bn.momentum)
+        std = torch.sqrt(var + bn.eps)
+        ctx.save_for_backward(x, mean, std, w, b)
+        ctx.whole_size, ctx.relu = n, relu
+        return native().bn_apply(x, mean, std, w, b, relu)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, mean, std, w, b = ctx.saved_tensors
+        dy = dy.contiguous()
+        dsum = native().bn_bwd_stats(dy, x, mean, std, w, b, ctx.relu)
+        _all_reduce_sum(dsum)
+        dx = native().bn_bwd_apply(dy, x, mean, std, w, b, dsum,
+                                   ctx.whole_size, ctx.relu)
+        return dx, dsum[1], dsum[0], None, None
+
+
+def sync_batch_norm_relu(x: torch.Tensor, bn, relu: bool) -> torch.Tensor:
+    """bn(x) [+ relu] for a models.sync_bn.SyncBatchNorm through the fused
+    gfx950 kernels: the GPU path (fp32 or bf16 [N, F]); CPU tensors keep
+    SyncBatchNorm.forward. Training normalises by the all-reduced batch
+    statistics over bn.whole_size rows and updates the running statistics;
+    eval (not bn.training) is the one bn_apply pass with the running
+    statistics, saves nothing and is not differentiable."""
+    if not x.is_cuda:
+        raise ValueError("sync_batch_norm_relu is the GPU path; on the CPU "
+                         "call the SyncBatchNorm module")
+    if x.dim() != 2 or x.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"sync_batch_norm_relu: x must be a fp32 or bf16 "
+                         f"[N, F] tensor, got {x.dtype} {tuple(x.shape)}")
+    # fp32 views, as in layer_norm_relu: bf16 params still receive grads
+    w, b = bn.weight.float(), bn.bias.float()
+    if bn.training:
+        return _SyncBatchNormReLU.apply(x, w, b, bn, relu)
+    with torch.no_grad():
+        std = torch.sqrt(bn.running_var.float() + bn.eps)
+        return native().bn_apply(x.contiguous(), bn.running_mean.float(),
+                                 std, w.contiguous(), b.contiguous(), relu)
+
+
 class _LinearColsum(torch.autograd.Function):
     """nn.Linear forward via rocBLAS with a colsum bias grad — torch's
     Linear backward picks a 1024-thread reduce for thin odd N (18.7 ms at

@@ -34,6 +34,7 @@ ext = CUDAExtension(
         "pipegcn_amd/csrc/hip/gatv2.hip",
         "pipegcn_amd/csrc/hip/dot_attn.hip",
         "pipegcn_amd/csrc/hip/gate.hip",
+        "pipegcn_amd/csrc/hip/batch_norm.hip",
     ],
     extra_compile_args={
         # -fopenmp: at::parallel_for is a header template — its OpenMP

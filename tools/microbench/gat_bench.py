@@ -54,6 +54,13 @@ model (forward 3 N F elements; backward 3 read + 2 written), and exits. With
 
     python tools/microbench/gat_bench.py --gate [--rounds 7 --iters 20]
     python tools/microbench/gat_bench.py --epoch --gate
+
+`--bn` times the four batch-norm kernels (csrc/hip/batch_norm.hip) on
+[num_in, F] rows, each against the bytes it must move, and
+ops.sync_batch_norm_relu forward and forward+backward against the eager
+composition (SyncBatchNorm's own forward, then relu), and exits.
+
+    python tools/microbench/gat_bench.py --bn --shape yelp --feats 512
 """
 import argparse
 import json
@@ -92,6 +99,8 @@ ap.add_argument("--edge-drop", "--edge_drop", type=float, default=0.0,
 ap.add_argument("--gate", action="store_true",
                 help="time the beta gate alone; with --epoch: the "
                      "Transformer without and with it")
+ap.add_argument("--bn", action="store_true",
+                help="time the fused batch-norm kernels alone")
 args = ap.parse_args()
 if args.pool and not args.epoch:
     ap.error("--pool times whole epochs: use it with --epoch")
@@ -186,6 +195,54 @@ def gate_bench():
                       for k, b in model.items()})), flush=True)
 
 
+def bn_bench():
+    from pipegcn_amd.models.sync_bn import SyncBatchNorm
+
+    N, nat = rp.num_in, native()
+    for dname in args.dtypes:
+        dtype = torch.bfloat16 if dname == "bf16" else torch.float32
+        es = 2 if dname == "bf16" else 4
+        gen = torch.Generator(device=dev).manual_seed(es)
+        x, g = (torch.randn(N, F, device=dev, generator=gen).to(dtype)
+                for _ in range(2))
+        bn = SyncBatchNorm(F, N).to(dev)
+        xr = x.clone().requires_grad_(True)
+        sums = nat.bn_stats(x)
+        mean = sums[0] / N
+        std = torch.sqrt((sums[1] - mean * sums[0]) / N + bn.eps)
+        w, b = bn.weight.detach(), bn.bias.detach()
+        dsum = nat.bn_bwd_stats(g, x, mean, std, w, b, True)
+
+        def fwd_bwd(f):
+            xr.grad = bn.weight.grad = bn.bias.grad = None
+            f(xr).backward(g)
+
+        samples = bench_rounds({
+            "bn_stats": lambda: nat.bn_stats(x),
+            "bn_apply": lambda: nat.bn_apply(x, mean, std, w, b, True),
+            "bn_bwd_stats": lambda: nat.bn_bwd_stats(g, x, mean, std, w, b,
+                                                     True),
+            "bn_bwd_apply": lambda: nat.bn_bwd_apply(g, x, mean, std, w, b,
+                                                     dsum, N, True),
+            "fused_fwd": lambda: ops.sync_batch_norm_relu(x, bn, True),
+            "eager_fwd": lambda: torch.relu(bn(x)),
+            "fused_fwd_bwd": lambda: fwd_bwd(
+                lambda t: ops.sync_batch_norm_relu(t, bn, True)),
+            "eager_fwd_bwd": lambda: fwd_bwd(lambda t: torch.relu(bn(t))),
+        })
+        ms = {k: [round(t, 3) for t in (min(v), statistics.median(v), max(v))]
+              for k, v in samples.items()}
+        # [N, F] passes each must make: reads + writes
+        passes = {"bn_stats": 1, "bn_apply": 2, "bn_bwd_stats": 2,
+                  "bn_bwd_apply": 3, "fused_fwd": 3, "fused_fwd_bwd": 8}
+        model = {k: p * N * F * es for k, p in passes.items()}
+        print(json.dumps(dict(
+            mode="bn", dtype=dname, N=N, F=F, ms_min_median_max=ms,
+            model_mb={k: round(v / 1e6, 1) for k, v in model.items()},
+            tb_per_s={k: round(v / ms[k][1] / 1e9, 3)
+                      for k, v in model.items()})), flush=True)
+
+
 def epoch_bench():
     import torch.nn.functional as Fn
 
@@ -274,6 +331,10 @@ if args.epoch:
 
 if args.gate:
     gate_bench()
+    sys.exit(0)
+
+if args.bn:
+    bn_bench()
     sys.exit(0)
 
 # (key, thr, scale) of the native entry points; (0, 0, 1.0) is no dropout
