@@ -64,13 +64,15 @@ def create_parser(argv=None):
                              "over the full-graph degrees (--model "
                              "graphsage with --aggregator mean, gcn; "
                              "refused with gat, gatv2 and transformer)")
-    parser.add_argument("--aggregator", choices=["mean", "pool"],
+    parser.add_argument("--aggregator", choices=["mean", "pool", "pna"],
                         default="mean",
                         help="neighbourhood aggregator of the GraphSAGE "
-                             "layers: mean, or max-pooling over projected "
-                             "and rectified neighbours (--model graphsage; "
-                             "pool does not combine with --use-pp; "
-                             "extension over the reference)")
+                             "layers: mean, max-pooling over projected "
+                             "and rectified neighbours, or pna: mean, max, "
+                             "min and standard deviation joined (--model "
+                             "graphsage; pool does not combine with "
+                             "--use-pp, pool and pna do not combine with "
+                             "--edge-drop; extensions over the reference)")
     parser.add_argument("--norm", choices=["layer", "batch", "none"],
                         default="layer", help="normalization method")
     parser.add_argument("--weight-decay", "--weight_decay", type=float,

@@ -98,6 +98,40 @@ static torch::Tensor spmm_max_bwd(torch::Tensor indptr, torch::Tensor indices,
   return max_aggregate_bwd_cpu(g, arg, num_src);
 }
 
+// GPU-only: ops.spmm_pna composes the CPU path from spmm, spmm_max and torch
+// -> [out] or, with_state, [out, arg, stat]
+static std::vector<torch::Tensor> spmm_pna(torch::Tensor indptr,
+                                           torch::Tensor indices,
+                                           torch::Tensor x,
+                                           torch::Tensor row_order,
+                                           int64_t num_rows, int64_t num_cols,
+                                           bool with_state) {
+  TORCH_CHECK(x.is_cuda(), "spmm_pna is the GPU path");
+  TORCH_CHECK(indptr.numel() == num_rows + 1,
+              "spmm_pna: indptr must hold num_rows + 1 entries");
+  return spmm_pna_fwd_hip(indptr, indices, x, row_order, num_cols,
+                          with_state);
+}
+
+static torch::Tensor pna_bwd_prep(torch::Tensor indptr, torch::Tensor g,
+                                  torch::Tensor stat) {
+  TORCH_CHECK(g.is_cuda(), "pna_bwd_prep is the GPU path");
+  return pna_bwd_prep_hip(indptr, g, stat);
+}
+
+// over the simple CSC (rows = the num_src sources)
+static torch::Tensor spmm_pna_bwd(torch::Tensor indptr, torch::Tensor indices,
+                                  torch::Tensor g, torch::Tensor arg,
+                                  torch::Tensor tt, torch::Tensor x,
+                                  torch::Tensor row_order, int64_t num_src,
+                                  int64_t num_cols) {
+  TORCH_CHECK(g.is_cuda(), "spmm_pna_bwd is the GPU path");
+  TORCH_CHECK(indptr.numel() == num_src + 1,
+              "spmm_pna_bwd: indptr must hold num_src + 1 entries");
+  return spmm_pna_bwd_hip(indptr, indices, g, arg, tt, x, row_order,
+                          num_cols);
+}
+
 // GPU-only (ops._SpmmMean.backward multiplies eagerly on the CPU)
 static std::vector<torch::Tensor> scale_rows_live(torch::Tensor g,
                                                   torch::Tensor inv) {
@@ -283,6 +317,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "grad_z of the max aggregation (GPU: over the simple CSC)",
         py::arg("indptr"), py::arg("indices"), py::arg("g"), py::arg("arg"),
         py::arg("row_order"), py::arg("num_src"), py::arg("num_cols"));
+  m.def("spmm_pna", &spmm_pna,
+        "mean/max/min/std aggregation over the CSR -> [out] or [out, arg, "
+        "stat]; out is [self | mean | max | min | std]",
+        py::arg("indptr"), py::arg("indices"), py::arg("x"),
+        py::arg("row_order"), py::arg("num_rows"), py::arg("num_cols"),
+        py::arg("with_state"));
+  m.def("pna_bwd_prep", &pna_bwd_prep,
+        "PQ = [g_mean / d - Q mean | Q = g_std rstd], fp32 [rows, 2F]",
+        py::arg("indptr"), py::arg("g"), py::arg("stat"));
+  m.def("spmm_pna_bwd", &spmm_pna_bwd,
+        "grad_x of the multi-aggregation over the simple CSC",
+        py::arg("indptr"), py::arg("indices"), py::arg("g"), py::arg("arg"),
+        py::arg("tt"), py::arg("x"), py::arg("row_order"),
+        py::arg("num_src"), py::arg("num_cols"));
   m.def("scale_rows_live", &scale_rows_live,
         "g * inv per row -> (scaled, n_live = 1 + last non-zero row, int32)");
   m.def("pack_rows", &pack_rows,

@@ -89,6 +89,37 @@ torch::Tensor spmm_max_bwd_hip(torch::Tensor indptr, torch::Tensor indices,
                                torch::Tensor g, torch::Tensor arg,
                                torch::Tensor row_order, int64_t num_cols);
 
+// Multi-aggregation (hip/spmm_pna.hip; docs/DESIGN.md, "Multi-aggregation
+// (PNA)"). x fp32 or bf16 [>= max(num_cols, num_rows), F]: destination r is
+// row r of x. -> {out} or, with_state, {out, arg, stat}:
+//   out  [num_rows, 5F] in x's dtype = [x[r] | mean | max | min | std] over
+//        the row's edges (parallel edges counted), std = sqrt(max(var, 0) +
+//        1e-5), zeros in the four statistic blocks of a row without edges;
+//   arg  int32 [num_rows, 2F] = [arg_max | arg_min] by spmm_max's first-edge
+//        rule, -1 on rows without edges;
+//   stat fp32 [num_rows, 2F] = [mean | rstd], rstd = 1 / (d * std), 0 where
+//        var <= 0 or the row has no edges.
+std::vector<torch::Tensor> spmm_pna_fwd_hip(torch::Tensor indptr,
+                                            torch::Tensor indices,
+                                            torch::Tensor x,
+                                            torch::Tensor row_order,
+                                            int64_t num_cols, bool with_state);
+// PQ = [P | Q] fp32 [num_rows, 2F] from g [>= num_rows, 5F] (the gradient of
+// out), stat and the CSR's row lengths: Q = g_std * rstd,
+// P = g_mean / d - Q * mean (0 on rows without edges).
+torch::Tensor pna_bwd_prep_hip(torch::Tensor indptr, torch::Tensor g,
+                               torch::Tensor stat);
+// indptr/indices/row_order are a CSC WITHOUT repeated entries (rows = sources
+// u, columns = destinations r < num_cols <= rows). grad_x[u,c] = sum over the
+// entries r of row u of g_max[r,c] where arg_max[r,c] == u and g_min[r,c]
+// where arg_min[r,c] == u, + tt[u,c] + x[u,c] * tt[u,F+c], + g_self[u,c]
+// where u < num_cols. tt fp32 [>= rows, 2F] is the transposed SpMM of PQ.
+// -> [rows, F] in x's dtype.
+torch::Tensor spmm_pna_bwd_hip(torch::Tensor indptr, torch::Tensor indices,
+                               torch::Tensor g, torch::Tensor arg,
+                               torch::Tensor tt, torch::Tensor x,
+                               torch::Tensor row_order, int64_t num_cols);
+
 // out[r,:] = scale[r] * sum_{e in [indptr[r], indptr[r+1])} feat[indices[e],:]
 // All tensors on device. feat fp32 [num_src, F], out fp32 [num_rows, F].
 // n_live (optional: undefined or empty is none; not with src_scale): one int32

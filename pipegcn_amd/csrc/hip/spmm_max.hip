@@ -34,6 +34,7 @@
 
 #include "../common.h"
 #include "attn_util.h"
+#include "gather_lanes.h"
 #include "hip_util.h"
 
 #include <hip/hip_bf16.h>
@@ -47,54 +48,10 @@
 namespace {
 
 // ld_vec / st_vec, for_edges and the host-side input checks are shared with
-// the attention kernels
+// the attention kernels; the id accesses, the scalar-register wave index, the
+// lane width and the launch geometry with spmm_pna.hip
 using namespace attn_util;
-
-// int32 ids, VEC per lane: one 4/8/16-byte access, or two 16-byte ones for
-// VEC = 8 (arg is 4 bytes per element whatever z's dtype is)
-template <int VEC>
-__device__ __forceinline__ void ld_ids(const int32_t* p, int32_t (&v)[VEC]) {
-  constexpr int W = VEC < 4 ? VEC : 4;
-  using R = typename raw_vec<4 * W>::type;
-#pragma unroll
-  for (int b = 0; b < VEC; b += W) {
-    const R r = *reinterpret_cast<const R*>(p + b);
-    __builtin_memcpy(&v[b], &r, sizeof(R));
-  }
-}
-
-template <int VEC>
-__device__ __forceinline__ void st_ids(int32_t* p, const int32_t (&v)[VEC]) {
-  constexpr int W = VEC < 4 ? VEC : 4;
-  using R = typename raw_vec<4 * W>::type;
-#pragma unroll
-  for (int b = 0; b < VEC; b += W) {
-    R r;
-    __builtin_memcpy(&r, &v[b], sizeof(R));
-    __builtin_nontemporal_store(r, reinterpret_cast<R*>(p + b));
-  }
-}
-
-// The wave of a (row, chunk) pair loop with its index in a scalar register,
-// as spmm_csr_kernel forms it: row, edge cursor and node ids are then
-// wave-uniform for the compiler too. The geometry arrives through default
-// arguments for the reason given at attn_util::wave_ids.
-struct UniformWave {
-  int64_t wave_global;
-  int lane;
-  int64_t nwaves;
-};
-
-__device__ __forceinline__ UniformWave uniform_wave(
-    unsigned block = blockIdx.x, unsigned block_dim = blockDim.x,
-    unsigned thread = threadIdx.x, unsigned grid_dim = gridDim.x) {
-  const int wave_in_block =
-      __builtin_amdgcn_readfirstlane(static_cast<int>(thread) / kWave);
-  const int64_t waves_per_block = block_dim / kWave;
-  return {static_cast<int64_t>(block) * waves_per_block + wave_in_block,
-          static_cast<int>(thread & (kWave - 1)),
-          static_cast<int64_t>(grid_dim) * waves_per_block};
-}
+using namespace gather_lanes;
 
 // ---------------------------------------------------------------------------
 // forward over the CSR (row = destination r, columns = sources u)
@@ -221,58 +178,6 @@ void check_arg(const torch::Tensor& arg, int64_t rows, int64_t F) {
               rows, " rows of width ", F);
 }
 
-// pick_vec's width, narrowed until every pointer takes the lane access:
-// `elems` hold `elem_size`-byte elements, `ids` int32 (16 bytes at the most
-// per access)
-int lane_vec(int64_t F, int64_t num_rows, int64_t elem_size,
-             std::initializer_list<const void*> elems, const void* ids) {
-  int vec = pick_vec(F, num_rows, elem_size);
-  auto fits = [&](int v) {
-    for (const void* p : elems)
-      if (!aligned_to(p, v * elem_size)) return false;
-    return ids == nullptr || aligned_to(ids, std::min(4 * v, 16));
-  };
-  while (vec > 1 && !fits(vec)) vec /= 2;
-  TORCH_CHECK(F % vec == 0 && vec * elem_size <= 16, kOp, ": lane width ",
-              vec, " does not fit rows of ", F, " elements");
-  return vec;
-}
-
-template <typename T>
-const T* cptr(const torch::Tensor& x) {
-  return reinterpret_cast<const T*>(x.data_ptr());
-}
-template <typename T>
-T* mptr(torch::Tensor& x) {
-  return reinterpret_cast<T*>(x.data_ptr());
-}
-
-// fn(T{}, VEC as an integral constant) for x's element type and a lane width
-// that lane_vec returned
-template <typename Fn>
-void dispatch(const torch::Tensor& x, int vec, Fn&& fn) {
-  dispatch_vec(vec, [&](auto v) {
-    if (x.scalar_type() == torch::kBFloat16) {
-      fn(__hip_bfloat16{}, v);
-    } else if constexpr (v.value <= 4) {
-      fn(float{}, v);
-    }
-  });
-}
-
-struct Launch {
-  int64_t nchunks;
-  dim3 grid, block;
-};
-
-Launch launch_of(int64_t num_rows, int64_t F, int vec) {
-  constexpr int threads = 256;  // whole waves: the kernels keep the wave
-  static_assert(threads % kWave == 0);  // index in a scalar register
-  const int64_t nchunks = (F + kWave * vec - 1) / (kWave * vec);
-  return {nchunks, dim3(grid_for(num_rows * nchunks, threads)),
-          dim3(threads)};
-}
-
 }  // namespace
 
 std::vector<torch::Tensor> spmm_max_fwd_hip(torch::Tensor indptr,
@@ -291,9 +196,9 @@ std::vector<torch::Tensor> spmm_max_fwd_hip(torch::Tensor indptr,
     arg = torch::empty({num_rows, F}, z.options().dtype(torch::kInt));
   if (num_rows > 0) {
     const int vec =
-        lane_vec(F, num_rows, z.element_size(),
+        lane_vec(kOp, F, num_rows, z.element_size(),
                  {z.data_ptr(), out.data_ptr()},
-                 with_arg ? arg.data_ptr() : nullptr);
+                 {with_arg ? arg.data_ptr() : nullptr});
     const Launch l = launch_of(num_rows, F, vec);
     dispatch(z, vec, [&](auto tag, auto v) {
       using T = decltype(tag);
@@ -328,8 +233,9 @@ torch::Tensor spmm_max_bwd_hip(torch::Tensor indptr, torch::Tensor indices,
   const int32_t* rop = row_order_ptr(kOp, row_order, num_rows);
   auto grad_z = torch::empty({num_rows, F}, g.options());
   if (num_rows == 0) return grad_z;
-  const int vec = lane_vec(F, num_rows, g.element_size(),
-                           {g.data_ptr(), grad_z.data_ptr()}, arg.data_ptr());
+  const int vec = lane_vec(kOp, F, num_rows, g.element_size(),
+                           {g.data_ptr(), grad_z.data_ptr()},
+                           {arg.data_ptr()});
   const Launch l = launch_of(num_rows, F, vec);
   dispatch(g, vec, [&](auto tag, auto v) {
     using T = decltype(tag);

@@ -11,7 +11,9 @@ HaloGraph/FullGraph CSR structures and hand-written gfx950 SpMM:
  - eval path: full homogeneous graph, degrees from the graph (layer.py:52-62);
  - init: uniform ±1/sqrt(fan_in) (layer.py:24-36);
  - `aggregator="pool"`: GraphSAGE's max-pooling aggregator (SAGEPoolLayer),
-   an extension over the reference, which has the mean only.
+   an extension over the reference, which has the mean only;
+ - `aggregator="pna"`: mean, max, min and standard deviation of the
+   neighbourhood joined (SAGEPNALayer), an extension as well.
 """
 from __future__ import annotations
 
@@ -157,6 +159,42 @@ class SAGEPoolLayer(nn.Module):
         return self.linear1(feat) + self.linear2(m)
 
 
+class SAGEPNALayer(nn.Module):
+    """Principal Neighbourhood Aggregation (Corso et al. 2020) with the
+    identity scaler: the node's own row joins the mean, maximum, minimum and
+    standard deviation of its neighbours, and one linear maps the lot:
+
+        out = linear([h[v] | mean | max | min | std over u in N(v)])
+
+    `ops.spmm_pna` forms the whole [.., 5 * in_feats] input in one gather
+    (csrc/hip/spmm_pna.hip). The neighbourhood term has no learned
+    projection, so a `use_pp` first layer takes that input precomputed
+    (`trainer.precompute`) and is its linear alone in training.
+    """
+
+    def __init__(self, in_feats, out_feats, bias=True, use_pp=False):
+        super().__init__()
+        self.use_pp = use_pp
+        self.linear = nn.Linear(5 * in_feats, out_feats, bias=bias)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        stdv = 1.0 / math.sqrt(self.linear.weight.size(1))
+        self.linear.weight.data.uniform_(-stdv, stdv)
+        if self.linear.bias is not None:
+            self.linear.bias.data.uniform_(-stdv, stdv)
+
+    def forward(self, graph, feat, in_deg=None):
+        if self.training:
+            if self.use_pp:
+                return ops.linear(feat, self.linear)
+            assert isinstance(graph, HaloGraph)
+            return ops.linear(ops.spmm_pna(graph, feat), self.linear)
+        # eval: full homogeneous graph, every node is a destination
+        assert isinstance(graph, FullGraph)
+        return self.linear(ops.spmm_pna_csr(graph.csr, feat))
+
+
 class GNNBase(nn.Module):
     """Conv layers, then `n_linear` linear layers, with norm + activation
     between layers; `ctx.buffer.update` is the only distributed seam.
@@ -249,7 +287,7 @@ class GNNBase(nn.Module):
         return self.activation(h)
 
 
-AGGREGATORS = ("mean", "pool")
+AGGREGATORS = ("mean", "pool", "pna")
 
 
 class GraphSAGE(GNNBase):
@@ -264,10 +302,10 @@ class GraphSAGE(GNNBase):
             # projection, so there is nothing to precompute
             raise NotImplementedError(
                 "--use-pp does not combine with --aggregator pool")
-        if check_edge_drop(edge_drop) > 0 and aggregator == "pool":
-            # a masked max gather does not exist (docs/ROADMAP.md)
+        if check_edge_drop(edge_drop) > 0 and aggregator in ("pool", "pna"):
+            # a masked max or multi gather does not exist (docs/ROADMAP.md)
             raise NotImplementedError(
-                "--edge-drop does not combine with --aggregator pool")
+                f"--edge-drop does not combine with --aggregator {aggregator}")
         super().__init__(layer_size, activation, dropout, norm, train_size,
                          n_linear, use_pp=use_pp, aggregator=aggregator,
                          edge_drop=edge_drop)
@@ -279,6 +317,11 @@ class GraphSAGE(GNNBase):
                   edge_drop):
         if aggregator == "pool":
             return SAGEPoolLayer(in_feats, out_feats)
+        if aggregator == "pna":
+            # use_pp: the first layer's input already holds
+            # [feat ‖ mean ‖ max ‖ min ‖ std], precomputed once
+            return SAGEPNALayer(in_feats, out_feats,
+                                use_pp=use_pp and i == 0)
         # use_pp applies to the first layer only: its input already holds
         # [feat ‖ mean_agg], precomputed once
         return GraphSAGELayer(in_feats, out_feats, use_pp=use_pp and i == 0,

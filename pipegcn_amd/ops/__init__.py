@@ -526,6 +526,147 @@ def spmm_max_csr(csr: CSR, z: torch.Tensor, with_arg: bool = False):
     return (res[0], res[1]) if with_arg else res[0]
 
 
+PNA_EPS = 1e-5  # PyG's PNAConv; csrc/hip/spmm_pna.hip holds the same value
+
+
+def _spmm_pna_check(csr: CSR, x: torch.Tensor) -> None:
+    """Raised before any launch."""
+    if x.dim() != 2 or x.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("spmm_pna: x must be a fp32 or bf16 [nodes, F] "
+                         f"tensor, got {tuple(x.shape)} {x.dtype}")
+    # destination r is row r of x: the self block reads it
+    need = max(csr.num_cols, csr.num_rows)
+    if x.shape[0] < need:
+        raise ValueError(
+            f"spmm_pna: x has {x.shape[0]} rows but the graph references "
+            f"{need} nodes (an under-sized x would be an out-of-bounds GPU "
+            "gather)")
+
+
+def _spmm_pna_cpu(csr: CSR, x: torch.Tensor, with_state: bool):
+    """The kernel's contract from what the CPU tier has: spmm for the sums,
+    the native spmm_max on x and -x for the extrema and their first-edge
+    args, torch for the epilogue. The sums are shifted by one value per
+    column (the column mean), which a plain SpMM can carry; the kernel
+    shifts by a row member."""
+    xf = x.float().contiguous()
+    n = csr.num_rows
+    d = csr.row_degrees().unsqueeze(1)
+    has, dc = d > 0, d.clamp(min=1.0)
+    c = xf[:max(csr.num_cols, 1)].mean(0, keepdim=True)
+    y = xf - c
+    m = spmm(csr, y) / dc
+    var = spmm(csr, y * y) / dc - m * m
+    std = torch.sqrt(torch.relu(var) + PNA_EPS)
+    mean = c + m
+    hi = native().spmm_max(csr.indptr, csr.indices, xf, torch.Tensor(), n,
+                           csr.num_cols, with_state)
+    lo = native().spmm_max(csr.indptr, csr.indices, -xf, torch.Tensor(), n,
+                           csr.num_cols, with_state)
+    zero = xf.new_zeros(())
+    out = torch.cat([xf[:n]] + [torch.where(has, t, zero)
+                                for t in (mean, hi[0], -lo[0], std)], dim=1)
+    if not with_state:
+        return [out.to(x.dtype)]
+    rstd = torch.where(has & (var > 0), 1.0 / (dc * std), zero)
+    return [out.to(x.dtype), torch.cat((hi[1], lo[1]), dim=1),
+            torch.cat((torch.where(has, mean, zero), rstd), dim=1)]
+
+
+def _spmm_pna_forward(csr: CSR, x: torch.Tensor, with_state: bool):
+    """[out] or [out, arg, stat] on x's device. Uses csr.row_order as given
+    (no lazy autotune here)."""
+    if not x.is_cuda:
+        return _spmm_pna_cpu(csr, x, with_state)
+    return native().spmm_pna(csr.indptr, csr.indices, x.contiguous(),
+                             _row_order(csr), csr.num_rows, csr.num_cols,
+                             with_state)
+
+
+class _SpmmPna(torch.autograd.Function):
+    """out[r] = [x[r] | mean | max | min | std] over the sources of r.
+
+    Saves x, the int32 [arg_max | arg_min] and the fp32 [mean | rstd], each
+    [num_in, 2F], and only when x wants a gradient. The backward is three
+    steps (docs/DESIGN.md, "Multi-aggregation (PNA)"): PQ per destination,
+    the dense transposed SpMM of PQ over the CSC (multiplicity counted), and
+    one gather over the simple CSC for the extrema, which also adds the
+    SpMM's term and the self block.
+    """
+
+    @staticmethod
+    def forward(ctx, graph: HaloGraph, x: torch.Tensor):
+        need_grad = ctx.needs_input_grad[1]
+        out, *state = _spmm_pna_forward(graph.csr, x, need_grad)
+        if need_grad:
+            ctx.save_for_backward(x, *state)
+        ctx.graph = graph
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, arg, stat = ctx.saved_tensors
+        graph, g = ctx.graph, g.contiguous()
+        F = x.shape[1]
+        if g.is_cuda:
+            pq = native().pna_bwd_prep(graph.csr.indptr, g, stat)
+            tt = spmm(graph.csc, pq, None)
+            csc = graph.csc_simple()
+            dx = native().spmm_pna_bwd(csc.indptr, csc.indices, g, arg, tt,
+                                       x.contiguous(), _row_order(csc),
+                                       csc.num_rows, csc.num_cols)
+        else:
+            g_self, g_mean, g_max, g_min, g_std = g.float().split(F, dim=1)
+            d = graph.csr.row_degrees().unsqueeze(1)
+            inv_d = torch.where(d > 0, 1.0 / d.clamp(min=1.0),
+                                torch.zeros_like(d))
+            q = g_std * stat[:, F:]
+            pq = torch.cat((g_mean * inv_d - q * stat[:, :F], q), dim=1)
+            tt = spmm(graph.csc, pq, None)
+            none, rows = torch.Tensor(), tt.shape[0]
+            dx = tt[:, :F] + x[:rows].float() * tt[:, F:]
+            for gk, ak in ((g_max, arg[:, :F]), (g_min, arg[:, F:])):
+                dx += native().spmm_max_bwd(none, none, gk.contiguous(),
+                                            ak.contiguous(), none, rows,
+                                            g.shape[0])
+            dx[:graph.num_in] += g_self
+            dx = dx.to(x.dtype)
+        if dx.shape[0] < x.shape[0]:  # rows the graph never references
+            dx = torch.cat((dx, dx.new_zeros(x.shape[0] - dx.shape[0], F)))
+        return None, dx
+
+
+def spmm_pna(graph: HaloGraph, x: torch.Tensor) -> torch.Tensor:
+    """Differentiable multi-aggregation (PNA) over the halo graph.
+
+    x [num_all, F], fp32 or bf16; returns [num_in, 5F] in x's dtype, laid out
+    [x[:num_in] | mean | max | min | std] over the sources of each
+    destination, parallel edges counted, std = sqrt(relu(var) + 1e-5). A
+    destination without edges gets zeros in the four statistic blocks. On the
+    GPU one kernel gathers every neighbour row once for all four. max and
+    min follow `spmm_max`'s contract: exact in both dtypes, and their
+    gradient goes to the source of the first edge, in CSR order, that attains
+    the extremum, once however many parallel edges there are. The gradient
+    through mean and std is formed as sum P + x * sum Q, which loses digits
+    when |mean| >> std (docs/DESIGN.md, "Multi-aggregation (PNA)"). NaN
+    inputs are unspecified.
+    """
+    _spmm_pna_check(graph.csr, x)
+    return _SpmmPna.apply(graph, x)
+
+
+def spmm_pna_csr(csr: CSR, x: torch.Tensor, with_state: bool = False):
+    """Forward-only multi-aggregation over a plain CSR (full-graph eval, the
+    --use-pp precompute). Returns out [num_rows, 5F], or (out, arg, stat)
+    with arg int32 [num_rows, 2F] = [arg_max | arg_min] (-1 on rows without
+    edges) and stat fp32 [num_rows, 2F] = [mean | rstd], rstd =
+    1 / (d * std), 0 where the variance is not positive."""
+    _spmm_pna_check(csr, x)
+    with torch.no_grad():
+        res = _spmm_pna_forward(csr, x, with_state)
+    return tuple(res) if with_state else res[0]
+
+
 def _gat_check(csr: CSR, z, el, er, num_heads: int) -> None:
     """Shape guards shared by both GAT paths; raised before any launch."""
     if num_heads < 1 or z.dim() != 2 or z.shape[1] % num_heads != 0:

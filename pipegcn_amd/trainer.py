@@ -168,6 +168,9 @@ def precompute(rp: RuntimePartition, args) -> torch.Tensor:
         # rows even with no peers — pad with zeros (an under-sized feat
         # tensor would be an out-of-bounds SpMM gather)
         feat_all = _pad_halo_zeros(rp, feat)
+    if getattr(args, "aggregator", "mean") == "pna":
+        # already [feat | mean | max | min | std]: layer 0 is its linear alone
+        return ops.spmm_pna_csr(rp.graph.csr, feat_all)
     inv_deg = (1.0 / rp.ndata["in_degree"].clamp(min=1.0)).contiguous()
     mean_feat = ops.spmm(rp.graph.csr, feat_all, inv_deg)
     return torch.cat([feat, mean_feat], dim=1)
@@ -176,10 +179,11 @@ def precompute(rp: RuntimePartition, args) -> torch.Tensor:
 def create_model(layer_size, args):
     aggregator = getattr(args, "aggregator", "mean")
     edge_drop = getattr(args, "edge_drop", 0.0)
-    if edge_drop > 0 and (aggregator == "pool"
+    if edge_drop > 0 and (aggregator in ("pool", "pna")
                           or args.model in ("gat", "gatv2", "transformer")):
-        # a masked max gather is a later item; attention has --attn-drop
-        what = ("--aggregator pool" if aggregator == "pool"
+        # a masked max or multi gather is a later item; attention has
+        # --attn-drop
+        what = (f"--aggregator {aggregator}" if aggregator in ("pool", "pna")
                 else f"--model {args.model}")
         raise NotImplementedError(
             f"--edge-drop does not combine with {what}")

@@ -61,6 +61,18 @@ ops.sync_batch_norm_relu forward and forward+backward against the eager
 composition (SyncBatchNorm's own forward, then relu), and exits.
 
     python tools/microbench/gat_bench.py --bn --shape yelp --feats 512
+
+`--pna` times the multi-aggregation (csrc/hip/spmm_pna.hip). Alone it times
+the fused forward with state against the composition it replaces (two mean
+SpMMs, on x and x^2, and spmm_max with its arg on x and -x; x^2 and -x are
+formed outside the window) and the three-step backward (prep, the transposed
+SpMM of PQ, spmm_pna_bwd) against two transposed SpMMs plus two
+spmm_max_bwd; it reports min / median / max over the rounds and logical
+bytes/s from the byte count of each, and exits. With `--epoch` it adds
+GraphSAGE with the pna aggregator, beside `--pool`.
+
+    python tools/microbench/gat_bench.py --pna --feats 602 [--rounds 7]
+    python tools/microbench/gat_bench.py --epoch --pool --pna
 """
 import argparse
 import json
@@ -101,6 +113,10 @@ ap.add_argument("--gate", action="store_true",
                      "Transformer without and with it")
 ap.add_argument("--bn", action="store_true",
                 help="time the fused batch-norm kernels alone")
+ap.add_argument("--pna", action="store_true",
+                help="time the multi-aggregation kernels against the "
+                     "composition they replace; with --epoch: GraphSAGE "
+                     "with the pna aggregator")
 args = ap.parse_args()
 if args.pool and not args.epoch:
     ap.error("--pool times whole epochs: use it with --epoch")
@@ -243,6 +259,70 @@ def bn_bench():
                       for k, v in model.items()})), flush=True)
 
 
+def pna_bench():
+    nat, n_in, n_all = native(), rp.num_in, rp.num_all
+    simple = hg.csc_simple()
+    none = torch.Tensor()
+    for dname in args.dtypes:
+        dtype = torch.bfloat16 if dname == "bf16" else torch.float32
+        es = 2 if dname == "bf16" else 4
+        gen = torch.Generator(device=dev).manual_seed(es)
+        x = torch.randn(n_all, F, device=dev, generator=gen).to(dtype)
+        g = torch.randn(n_in, 5 * F, device=dev, generator=gen).to(dtype)
+        x2, nx = x * x, -x
+        gm, gs, gmax, gmin = (g[:, k * F:(k + 1) * F].contiguous()
+                              for k in (1, 4, 2, 3))
+        _, arg, stat = ops.spmm_pna_csr(csr, x, with_state=True)
+        amax, amin = (a.contiguous() for a in arg.split(F, dim=1))
+
+        def fused_bwd():
+            pq = nat.pna_bwd_prep(csr.indptr, g, stat)
+            tt = ops.spmm(csc, pq, None)
+            return nat.spmm_pna_bwd(simple.indptr, simple.indices, g, arg, tt,
+                                    x, ops._row_order(simple),
+                                    simple.num_rows, simple.num_cols)
+
+        def max_bwd(gk, ak):
+            return nat.spmm_max_bwd(simple.indptr, simple.indices, gk, ak,
+                                    ops._row_order(simple), simple.num_rows,
+                                    simple.num_cols)
+
+        samples = bench_rounds({
+            "fused_fwd": lambda: ops.spmm_pna_csr(csr, x, with_state=True),
+            "comp_fwd": lambda: (
+                ops.spmm(csr, x, inv), ops.spmm(csr, x2, inv),
+                ops.spmm_max_csr(csr, x, with_arg=True),
+                ops.spmm_max_csr(csr, nx, with_arg=True)),
+            "fused_bwd": fused_bwd,
+            "comp_bwd": lambda: (
+                ops.spmm(csc, gm, None), ops.spmm(csc, gs, None),
+                max_bwd(gmax, amax), max_bwd(gmin, amin)),
+        })
+        ms = {k: [round(t, 3) for t in (min(v), statistics.median(v), max(v))]
+              for k, v in samples.items()}
+        # logical bytes: per edge the index and the gathered rows, per row
+        # what is read and written once
+        e2 = simple.nnz
+        model = {
+            "fused_fwd": nnz * (es * F + 4) + n_in * F * (6 * es + 16),
+            "comp_fwd": 4 * nnz * (es * F + 4) + n_in * F * (4 * es + 8),
+            "fused_bwd": (n_in * F * (2 * es + 16)
+                          + nnz * (8 * F + 4) + n_all * 8 * F
+                          + e2 * ((2 * es + 8) * F + 4)
+                          + n_all * F * (2 * es + 8)),
+            "comp_bwd": (2 * nnz * (es * F + 4)
+                         + 2 * e2 * ((es + 4) * F + 4) + 4 * n_all * F * es),
+        }
+        print(json.dumps(dict(
+            mode="pna", shape=args.shape, dtype=dname, F=F, nnz=nnz,
+            nnz_simple=e2, ms_min_median_max=ms,
+            fwd_ratio=round(ms["fused_fwd"][1] / ms["comp_fwd"][1], 3),
+            bwd_ratio=round(ms["fused_bwd"][1] / ms["comp_bwd"][1], 3),
+            model_gb={k: round(b / 1e9, 2) for k, b in model.items()},
+            tb_per_s={k: round(b / ms[k][1] / 1e9, 3)
+                      for k, b in model.items()})), flush=True)
+
+
 def epoch_bench():
     import torch.nn.functional as Fn
 
@@ -276,6 +356,9 @@ def epoch_bench():
         if args.pool:
             models.append(("graphsage-pool", GraphSAGE,
                            dict(use_pp=False, aggregator="pool"), deg))
+        if args.pna:
+            models.append(("graphsage-pna", GraphSAGE,
+                           dict(use_pp=False, aggregator="pna"), deg))
         if args.edge_drop > 0:
             models.append(("graphsage-edge-drop", GraphSAGE,
                            dict(use_pp=False, edge_drop=args.edge_drop), deg))
@@ -335,6 +418,10 @@ if args.gate:
 
 if args.bn:
     bn_bench()
+    sys.exit(0)
+
+if args.pna:
+    pna_bench()
     sys.exit(0)
 
 # (key, thr, scale) of the native entry points; (0, 0, 1.0) is no dropout
