@@ -64,15 +64,19 @@ def create_parser(argv=None):
                              "over the full-graph degrees (--model "
                              "graphsage with --aggregator mean, gcn; "
                              "refused with gat, gatv2 and transformer)")
-    parser.add_argument("--aggregator", choices=["mean", "pool", "pna"],
+    parser.add_argument("--aggregator",
+                        choices=["mean", "pool", "pna", "softmax"],
                         default="mean",
                         help="neighbourhood aggregator of the GraphSAGE "
                              "layers: mean, max-pooling over projected "
-                             "and rectified neighbours, or pna: mean, max, "
-                             "min and standard deviation joined (--model "
-                             "graphsage; pool does not combine with "
-                             "--use-pp, pool and pna do not combine with "
-                             "--edge-drop; extensions over the reference)")
+                             "and rectified neighbours, pna: mean, max, "
+                             "min and standard deviation joined, or "
+                             "softmax: DeeperGCN's softmax aggregation with "
+                             "a learned inverse temperature per layer "
+                             "(--model graphsage; pool and softmax do not "
+                             "combine with --use-pp, pool, pna and softmax "
+                             "do not combine with --edge-drop; extensions "
+                             "over the reference)")
     parser.add_argument("--norm", choices=["layer", "batch", "none"],
                         default="layer", help="normalization method")
     parser.add_argument("--weight-decay", "--weight_decay", type=float,

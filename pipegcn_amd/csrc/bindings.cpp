@@ -132,6 +132,33 @@ static torch::Tensor spmm_pna_bwd(torch::Tensor indptr, torch::Tensor indices,
                           num_cols);
 }
 
+// GPU-only: ops.spmm_softmax composes the CPU path from torch ops
+// -> [out] or, with_state, [out, lse] (fp32) / [out, lse, out32] (bf16)
+static std::vector<torch::Tensor> spmm_softmax(
+    torch::Tensor indptr, torch::Tensor indices, torch::Tensor x,
+    torch::Tensor beta, torch::Tensor row_order, int64_t num_rows,
+    int64_t num_cols, bool with_state) {
+  TORCH_CHECK(x.is_cuda(), "spmm_softmax is the GPU path");
+  TORCH_CHECK(indptr.numel() == num_rows + 1,
+              "spmm_softmax: indptr must hold num_rows + 1 entries");
+  return spmm_softmax_fwd_hip(indptr, indices, x, beta, row_order, num_cols,
+                              with_state);
+}
+
+// over the CSC with repeated entries (rows = the num_src sources)
+// -> [grad_x, dbeta]
+static std::vector<torch::Tensor> spmm_softmax_bwd(
+    torch::Tensor indptr, torch::Tensor indices, torch::Tensor g,
+    torch::Tensor lse, torch::Tensor out32, torch::Tensor x,
+    torch::Tensor beta, torch::Tensor row_order, int64_t num_src,
+    int64_t num_cols) {
+  TORCH_CHECK(g.is_cuda(), "spmm_softmax_bwd is the GPU path");
+  TORCH_CHECK(indptr.numel() == num_src + 1,
+              "spmm_softmax_bwd: indptr must hold num_src + 1 entries");
+  return spmm_softmax_bwd_hip(indptr, indices, g, lse, out32, x, beta,
+                              row_order, num_cols);
+}
+
 // GPU-only (ops._SpmmMean.backward multiplies eagerly on the CPU)
 static std::vector<torch::Tensor> scale_rows_live(torch::Tensor g,
                                                   torch::Tensor inv) {
@@ -331,6 +358,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("indptr"), py::arg("indices"), py::arg("g"), py::arg("arg"),
         py::arg("tt"), py::arg("x"), py::arg("row_order"),
         py::arg("num_src"), py::arg("num_cols"));
+  m.def("spmm_softmax", &spmm_softmax,
+        "softmax aggregation over the CSR -> [out] or [out, lse(, out32)]; "
+        "lse is in base 2",
+        py::arg("indptr"), py::arg("indices"), py::arg("x"), py::arg("beta"),
+        py::arg("row_order"), py::arg("num_rows"), py::arg("num_cols"),
+        py::arg("with_state"));
+  m.def("spmm_softmax_bwd", &spmm_softmax_bwd,
+        "[grad_x, dbeta] of the softmax aggregation over the CSC",
+        py::arg("indptr"), py::arg("indices"), py::arg("g"), py::arg("lse"),
+        py::arg("out32"), py::arg("x"), py::arg("beta"),
+        py::arg("row_order"), py::arg("num_src"), py::arg("num_cols"));
   m.def("scale_rows_live", &scale_rows_live,
         "g * inv per row -> (scaled, n_live = 1 + last non-zero row, int32)");
   m.def("pack_rows", &pack_rows,

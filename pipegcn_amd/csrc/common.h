@@ -120,6 +120,33 @@ torch::Tensor spmm_pna_bwd_hip(torch::Tensor indptr, torch::Tensor indices,
                                torch::Tensor tt, torch::Tensor x,
                                torch::Tensor row_order, int64_t num_cols);
 
+// Softmax aggregation (hip/spmm_softmax.hip; docs/DESIGN.md, "Softmax
+// aggregation"). x fp32 or bf16 [>= num_cols, F], beta one fp32 value in
+// device memory. -> {out} or, with_state, {out, lse} (fp32 x) or
+// {out, lse, out32} (bf16 x):
+//   out   [num_rows, F] in x's dtype, out[r,c] = sum_u softmax_u(beta x[u,c])
+//         x[u,c] over the row's edges (parallel edges counted), 0 on a row
+//         without edges;
+//   lse   fp32 [num_rows, F], IN BASE 2: the weight of edge u -> r is
+//         exp2(beta log2(e) x[u,c] - lse[r,c]); 0 on a row without edges;
+//   out32 fp32 [num_rows, F]: out before its rounding to bf16.
+std::vector<torch::Tensor> spmm_softmax_fwd_hip(
+    torch::Tensor indptr, torch::Tensor indices, torch::Tensor x,
+    torch::Tensor beta, torch::Tensor row_order, int64_t num_cols,
+    bool with_state);
+// indptr/indices/row_order are the CSC WITH repeated entries (rows = sources
+// j, columns = destinations i < num_cols). g in x's dtype, lse and out32 fp32,
+// each [>= num_cols, F] (for fp32 x, out32 is out itself); x [>= rows, F].
+// With w = weight of the entry, gw = g[i,c] w and t = x[j,c] - out32[i,c]:
+//   grad_x[j,c] = sum_i gw (1 + beta t)      -> [rows, F] in x's dtype
+//   dbeta       = sum_{j,i,c} gw t x[j,c]    -> fp32 [1], summed in a fixed
+//                                               order
+// -> {grad_x, dbeta}.
+std::vector<torch::Tensor> spmm_softmax_bwd_hip(
+    torch::Tensor indptr, torch::Tensor indices, torch::Tensor g,
+    torch::Tensor lse, torch::Tensor out32, torch::Tensor x,
+    torch::Tensor beta, torch::Tensor row_order, int64_t num_cols);
+
 // out[r,:] = scale[r] * sum_{e in [indptr[r], indptr[r+1])} feat[indices[e],:]
 // All tensors on device. feat fp32 [num_src, F], out fp32 [num_rows, F].
 // n_live (optional: undefined or empty is none; not with src_scale): one int32

@@ -13,7 +13,9 @@ HaloGraph/FullGraph CSR structures and hand-written gfx950 SpMM:
  - `aggregator="pool"`: GraphSAGE's max-pooling aggregator (SAGEPoolLayer),
    an extension over the reference, which has the mean only;
  - `aggregator="pna"`: mean, max, min and standard deviation of the
-   neighbourhood joined (SAGEPNALayer), an extension as well.
+   neighbourhood joined (SAGEPNALayer), an extension as well;
+ - `aggregator="softmax"`: DeeperGCN's learnable softmax aggregation in the
+   mean's place (SAGESoftmaxLayer), an extension as well.
 """
 from __future__ import annotations
 
@@ -195,6 +197,60 @@ class SAGEPNALayer(nn.Module):
         return self.linear(ops.spmm_pna_csr(graph.csr, feat))
 
 
+class SAGESoftmaxLayer(nn.Module):
+    """GraphSAGE with the learnable softmax aggregation of DeeperGCN (PyG's
+    SoftmaxAggregation(learn=True)) in the mean's place:
+
+        s[v, c] = sum_u softmax_u(beta * h[u, c]) * h[u, c]   over u in N(v)
+        out = linear1(h[:num_dst]) + linear2(s)
+
+    beta is one learned inverse temperature per layer, initialised to 1:
+    0 is the mean, large |beta| approaches max or min. `ops.spmm_softmax` is
+    the aggregation (csrc/hip/spmm_softmax.hip). beta and its gradient stay
+    fp32 when the module is cast to bf16.
+    """
+
+    def __init__(self, in_feats, out_feats, bias=True):
+        super().__init__()
+        self.linear1 = nn.Linear(in_feats, out_feats, bias=bias)
+        self.linear2 = nn.Linear(in_feats, out_feats, bias=bias)
+        self.beta = nn.Parameter(torch.ones(1))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        # GraphSAGELayer's draws, in its order; beta draws nothing
+        for lin in (self.linear1, self.linear2):
+            stdv = 1.0 / math.sqrt(lin.weight.size(1))
+            lin.weight.data.uniform_(-stdv, stdv)
+            if lin.bias is not None:
+                lin.bias.data.uniform_(-stdv, stdv)
+        self.beta.data.fill_(1.0)
+
+    def _apply(self, fn, *args, **kwargs):
+        super()._apply(fn, *args, **kwargs)
+        if self.beta.dtype != torch.float32:  # a cast of the module
+            grad = self.beta.grad
+            self.beta.grad = None
+            self.beta.data = self.beta.data.float()
+            if grad is not None:
+                self.beta.grad = grad.float()
+        return self
+
+    def forward(self, graph, feat, in_deg=None):
+        if self.training:
+            assert isinstance(graph, HaloGraph)
+            s = ops.spmm_softmax(graph, feat, self.beta)
+            x1 = feat[: graph.num_in]
+            if feat.is_cuda:
+                return ops.sage_dual_linear(x1, s, self.linear1,
+                                            self.linear2)
+            return self.linear1(x1) + self.linear2(s)
+        # eval: full homogeneous graph, every node is a destination
+        assert isinstance(graph, FullGraph)
+        s = ops.spmm_softmax_csr(graph.csr, feat, self.beta)
+        return self.linear1(feat) + self.linear2(s)
+
+
 class GNNBase(nn.Module):
     """Conv layers, then `n_linear` linear layers, with norm + activation
     between layers; `ctx.buffer.update` is the only distributed seam.
@@ -287,7 +343,7 @@ class GNNBase(nn.Module):
         return self.activation(h)
 
 
-AGGREGATORS = ("mean", "pool", "pna")
+AGGREGATORS = ("mean", "pool", "pna", "softmax")
 
 
 class GraphSAGE(GNNBase):
@@ -302,8 +358,14 @@ class GraphSAGE(GNNBase):
             # projection, so there is nothing to precompute
             raise NotImplementedError(
                 "--use-pp does not combine with --aggregator pool")
-        if check_edge_drop(edge_drop) > 0 and aggregator in ("pool", "pna"):
-            # a masked max or multi gather does not exist (docs/ROADMAP.md)
+        if use_pp and aggregator == "softmax":
+            # layer 0's aggregate depends on a learned beta
+            raise NotImplementedError(
+                "--use-pp does not combine with --aggregator softmax")
+        if check_edge_drop(edge_drop) > 0 and aggregator in ("pool", "pna",
+                                                             "softmax"):
+            # a masked max, multi or softmax gather does not exist
+            # (docs/ROADMAP.md)
             raise NotImplementedError(
                 f"--edge-drop does not combine with --aggregator {aggregator}")
         super().__init__(layer_size, activation, dropout, norm, train_size,
@@ -322,6 +384,8 @@ class GraphSAGE(GNNBase):
             # [feat ‖ mean ‖ max ‖ min ‖ std], precomputed once
             return SAGEPNALayer(in_feats, out_feats,
                                 use_pp=use_pp and i == 0)
+        if aggregator == "softmax":
+            return SAGESoftmaxLayer(in_feats, out_feats)
         # use_pp applies to the first layer only: its input already holds
         # [feat ‖ mean_agg], precomputed once
         return GraphSAGELayer(in_feats, out_feats, use_pp=use_pp and i == 0,

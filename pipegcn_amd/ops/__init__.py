@@ -873,6 +873,108 @@ def _edge_softmax_aggregate_torch(csr: CSR, u, v, score, values, drop=None):
     return out.view(rows, -1)
 
 
+def _spmm_softmax_check(csr: CSR, x: torch.Tensor, beta: torch.Tensor) -> None:
+    """Raised before any launch."""
+    if x.dim() != 2 or x.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("spmm_softmax: x must be a fp32 or bf16 [nodes, F] "
+                         f"tensor, got {tuple(x.shape)} {x.dtype}")
+    if x.shape[0] < csr.num_cols:
+        raise ValueError(
+            f"spmm_softmax: x has {x.shape[0]} rows but the graph references "
+            f"{csr.num_cols} source nodes (an under-sized x would be an "
+            "out-of-bounds GPU gather)")
+    if (beta.numel() != 1 or beta.dtype != torch.float32
+            or beta.device != x.device):
+        raise ValueError("spmm_softmax: beta must be one fp32 value on x's "
+                         f"device, got {tuple(beta.shape)} {beta.dtype} on "
+                         f"{beta.device}")
+
+
+def _spmm_softmax_torch(csr: CSR, x, beta):
+    """The softmax aggregation composed from torch ops under ordinary
+    autograd: the CPU test tier and rank-0 eval. Every column is a head of
+    width 1 whose score is beta times its value. [nnz, F] temporaries are
+    fine here; the GPU path never makes them."""
+    u, v = _edge_endpoints(csr)
+    xu = x.float().index_select(0, u)
+    out = _edge_softmax_aggregate_torch(csr, u, v, beta.view(1, 1) * xu,
+                                        xu.unsqueeze(-1))
+    return out.to(x.dtype)
+
+
+def _spmm_softmax_forward_hip(csr: CSR, x, beta, with_state: bool):
+    """[out] or [out, lse(, out32)] on the gfx950 kernel. Uses csr.row_order
+    as given (no lazy autotune here)."""
+    return native().spmm_softmax(csr.indptr, csr.indices, x.contiguous(),
+                                 beta, _row_order(csr), csr.num_rows,
+                                 csr.num_cols, with_state)
+
+
+class _SpmmSoftmax(torch.autograd.Function):
+    """out[r] = sum_u softmax_u(beta x[u]) x[u] per column (GPU).
+
+    Saves x, beta, the fp32 lse [num_in, F] (in base 2) and the fp32 output
+    (out itself at fp32, its unrounded copy at bf16), and only when a
+    gradient is wanted. The backward is ONE gather over the CSC with its
+    repeated entries, which recomputes every weight from them and yields
+    grad_x and grad_beta together (docs/DESIGN.md, "Softmax aggregation").
+    """
+
+    @staticmethod
+    def forward(ctx, graph: HaloGraph, x: torch.Tensor, beta: torch.Tensor):
+        need_grad = any(ctx.needs_input_grad)
+        out, *state = _spmm_softmax_forward_hip(graph.csr, x, beta, need_grad)
+        if need_grad:
+            lse, out32 = state if len(state) == 2 else (state[0], out)
+            ctx.save_for_backward(x, beta, lse, out32)
+        ctx.graph = graph
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, beta, lse, out32 = ctx.saved_tensors
+        csc = ctx.graph.csc
+        dx, dbeta = native().spmm_softmax_bwd(
+            csc.indptr, csc.indices, g.contiguous(), lse, out32,
+            x.contiguous(), beta, _row_order(csc), csc.num_rows, csc.num_cols)
+        if dx.shape[0] < x.shape[0]:  # rows the graph never references
+            dx = torch.cat((dx, dx.new_zeros(x.shape[0] - dx.shape[0],
+                                             dx.shape[1])))
+        return None, dx, dbeta.view(beta.shape)
+
+
+def spmm_softmax(graph: HaloGraph, x: torch.Tensor,
+                 beta: torch.Tensor) -> torch.Tensor:
+    """Differentiable softmax aggregation (DeeperGCN's, PyG's
+    SoftmaxAggregation(learn=True)) over the halo graph.
+
+    x [num_all, F], fp32 or bf16; beta one fp32 value on x's device, the
+    learned inverse temperature. Returns out [num_in, F] in x's dtype with
+    out[r, c] = sum_u softmax_u(beta * x[u, c]) * x[u, c] over the sources u
+    of r, every column with a softmax of its own, parallel edges counted,
+    and 0 for a destination without edges. beta = 0 is the mean; large
+    |beta| approaches the maximum or the minimum. Differentiable in x and in
+    beta; beta's gradient is fp32 whatever x's dtype is. On the GPU each
+    pass is one gather and nothing of size nnz is allocated; out and grad_x
+    do not depend on the row order (docs/DESIGN.md, "Softmax aggregation").
+    """
+    _spmm_softmax_check(graph.csr, x, beta)
+    if not x.is_cuda:
+        return _spmm_softmax_torch(graph.csr, x, beta)
+    return _SpmmSoftmax.apply(graph, x, beta)
+
+
+def spmm_softmax_csr(csr: CSR, x: torch.Tensor,
+                     beta: torch.Tensor) -> torch.Tensor:
+    """Forward-only softmax aggregation over a plain CSR (full-graph eval
+    over FullGraph.csr)."""
+    _spmm_softmax_check(csr, x, beta)
+    with torch.no_grad():
+        if not x.is_cuda:
+            return _spmm_softmax_torch(csr, x, beta)
+        return _spmm_softmax_forward_hip(csr, x, beta, False)[0]
+
+
 def _gat_aggregate_torch(csr: CSR, z, el, er, num_heads: int, slope: float,
                          drop=None):
     """Edge-softmax aggregation composed from torch ops under ordinary

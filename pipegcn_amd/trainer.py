@@ -146,6 +146,10 @@ def precompute(rp: RuntimePartition, args) -> torch.Tensor:
         # layer 0's neighbourhood term passes through a learned projection
         raise NotImplementedError(
             "--use-pp does not combine with --aggregator pool")
+    if getattr(args, "aggregator", "mean") == "softmax":
+        # layer 0's aggregate depends on a learned beta
+        raise NotImplementedError(
+            "--use-pp does not combine with --aggregator softmax")
     feat = rp.ndata["feat"]
     size = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
@@ -179,11 +183,12 @@ def precompute(rp: RuntimePartition, args) -> torch.Tensor:
 def create_model(layer_size, args):
     aggregator = getattr(args, "aggregator", "mean")
     edge_drop = getattr(args, "edge_drop", 0.0)
-    if edge_drop > 0 and (aggregator in ("pool", "pna")
+    unmasked = ("pool", "pna", "softmax")
+    if edge_drop > 0 and (aggregator in unmasked
                           or args.model in ("gat", "gatv2", "transformer")):
-        # a masked max or multi gather is a later item; attention has
-        # --attn-drop
-        what = (f"--aggregator {aggregator}" if aggregator in ("pool", "pna")
+        # a masked max, multi or softmax gather is a later item; attention
+        # has --attn-drop
+        what = (f"--aggregator {aggregator}" if aggregator in unmasked
                 else f"--model {args.model}")
         raise NotImplementedError(
             f"--edge-drop does not combine with {what}")

@@ -26,6 +26,7 @@ ext = CUDAExtension(
         "pipegcn_amd/csrc/hip/spmm_packed_bf16.hip",
         "pipegcn_amd/csrc/hip/spmm_max.hip",
         "pipegcn_amd/csrc/hip/spmm_pna.hip",
+        "pipegcn_amd/csrc/hip/spmm_softmax.hip",
         "pipegcn_amd/csrc/hip/spmm_drop.hip",
         "pipegcn_amd/csrc/hip/dual_gemm.hip",
         "pipegcn_amd/csrc/hip/elementwise.hip",

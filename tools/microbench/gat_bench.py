@@ -73,6 +73,15 @@ GraphSAGE with the pna aggregator, beside `--pool`.
 
     python tools/microbench/gat_bench.py --pna --feats 602 [--rounds 7]
     python tools/microbench/gat_bench.py --epoch --pool --pna
+
+`--softmax` times the softmax aggregation (csrc/hip/spmm_softmax.hip): its
+forward with state against the mean SpMM forward on the same graph and width,
+and its backward against the transposed SpMM; min / median / max over the
+rounds, logical bytes/s, and exits. With `--epoch` it adds GraphSAGE with the
+softmax aggregator.
+
+    python tools/microbench/gat_bench.py --softmax --feats 602 [--rounds 7]
+    python tools/microbench/gat_bench.py --epoch --softmax
 """
 import argparse
 import json
@@ -117,6 +126,10 @@ ap.add_argument("--pna", action="store_true",
                 help="time the multi-aggregation kernels against the "
                      "composition they replace; with --epoch: GraphSAGE "
                      "with the pna aggregator")
+ap.add_argument("--softmax", action="store_true",
+                help="time the softmax aggregation kernels against the mean "
+                     "SpMM and its transpose; with --epoch: GraphSAGE with "
+                     "the softmax aggregator")
 args = ap.parse_args()
 if args.pool and not args.epoch:
     ap.error("--pool times whole epochs: use it with --epoch")
@@ -323,6 +336,51 @@ def pna_bench():
                       for k, b in model.items()})), flush=True)
 
 
+def softmax_bench():
+    nat, n_in, n_all = native(), rp.num_in, rp.num_all
+    for dname in args.dtypes:
+        dtype = torch.bfloat16 if dname == "bf16" else torch.float32
+        es = 2 if dname == "bf16" else 4
+        gen = torch.Generator(device=dev).manual_seed(es)
+        x = torch.randn(n_all, F, device=dev, generator=gen).to(dtype)
+        g = torch.randn(n_in, F, device=dev, generator=gen).to(dtype)
+        beta = torch.ones(1, device=dev)
+        out, lse, *o32 = nat.spmm_softmax(
+            csr.indptr, csr.indices, x, beta, ops._row_order(csr),
+            csr.num_rows, csr.num_cols, True)
+        out32 = o32[0] if o32 else out
+
+        samples = bench_rounds({
+            "softmax_fwd": lambda: nat.spmm_softmax(
+                csr.indptr, csr.indices, x, beta, ops._row_order(csr),
+                csr.num_rows, csr.num_cols, True),
+            "mean_fwd": lambda: ops.spmm(csr, x, inv),
+            "softmax_bwd": lambda: nat.spmm_softmax_bwd(
+                csc.indptr, csc.indices, g, lse, out32, x, beta,
+                ops._row_order(csc), csc.num_rows, csc.num_cols),
+            "mean_bwd": lambda: ops.spmm(csc, g, None),
+        })
+        ms = {k: [round(t, 3) for t in (min(v), statistics.median(v), max(v))]
+              for k, v in samples.items()}
+        # logical bytes: per edge the index and the gathered rows, per row
+        # what is read and written once
+        state = 4 if es == 4 else 8  # lse, and out32 at bf16
+        model = {
+            "softmax_fwd": nnz * (es * F + 4) + n_in * F * (es + state),
+            "mean_fwd": nnz * (es * F + 4) + n_in * F * es,
+            "softmax_bwd": nnz * ((es + 8) * F + 4) + 2 * n_all * F * es,
+            "mean_bwd": nnz * (es * F + 4) + n_all * F * es,
+        }
+        print(json.dumps(dict(
+            mode="softmax", shape=args.shape, dtype=dname, F=F, nnz=nnz,
+            ms_min_median_max=ms,
+            fwd_ratio=round(ms["softmax_fwd"][1] / ms["mean_fwd"][1], 3),
+            bwd_ratio=round(ms["softmax_bwd"][1] / ms["mean_bwd"][1], 3),
+            model_gb={k: round(b / 1e9, 2) for k, b in model.items()},
+            tb_per_s={k: round(b / ms[k][1] / 1e9, 3)
+                      for k, b in model.items()})), flush=True)
+
+
 def epoch_bench():
     import torch.nn.functional as Fn
 
@@ -359,6 +417,9 @@ def epoch_bench():
         if args.pna:
             models.append(("graphsage-pna", GraphSAGE,
                            dict(use_pp=False, aggregator="pna"), deg))
+        if args.softmax:
+            models.append(("graphsage-softmax", GraphSAGE,
+                           dict(use_pp=False, aggregator="softmax"), deg))
         if args.edge_drop > 0:
             models.append(("graphsage-edge-drop", GraphSAGE,
                            dict(use_pp=False, edge_drop=args.edge_drop), deg))
@@ -422,6 +483,10 @@ if args.bn:
 
 if args.pna:
     pna_bench()
+    sys.exit(0)
+
+if args.softmax:
+    softmax_bench()
     sys.exit(0)
 
 # (key, thr, scale) of the native entry points; (0, 0, 1.0) is no dropout
