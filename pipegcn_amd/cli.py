@@ -2,6 +2,11 @@
 (/root/reference/helper/parser.py:4-71), including dual dash/underscore
 spellings and defaults. `--norm none` is normalized to None by check_args
 (reference train.py:403-405).
+
+`--model` takes the reference's graphsage and, as extensions, gcn, gat, gatv2,
+transformer and resgated (the residual gated graph conv; it reads neither
+`--n-heads` nor `--attn-drop` and refuses `--use-pp`, `--edge-drop`,
+`--beta-gate` and `--aggregator` other than mean).
 """
 import argparse
 
@@ -22,7 +27,8 @@ def create_parser(argv=None):
 
     parser.add_argument("--model", type=str, default="graphsage",
                         help="model for training: graphsage, gcn, gat, "
-                             "gatv2 or transformer")
+                             "gatv2, transformer or resgated (the residual "
+                             "gated graph conv)")
     parser.add_argument("--dropout", type=float, default=0.5,
                         help="dropout probability")
     parser.add_argument("--lr", type=float, default=1e-2,
@@ -63,7 +69,8 @@ def create_parser(argv=None):
                              "in training, the kept sum scaled by 1/(1-p) "
                              "over the full-graph degrees (--model "
                              "graphsage with --aggregator mean, gcn; "
-                             "refused with gat, gatv2 and transformer)")
+                             "refused with gat, gatv2, transformer and "
+                             "resgated)")
     parser.add_argument("--aggregator",
                         choices=["mean", "pool", "pna", "softmax"],
                         default="mean",

@@ -461,6 +461,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("num_cols"), py::arg("num_heads"), py::arg("scale"),
         py::arg("drop_key") = 0, py::arg("drop_thr") = 0,
         py::arg("drop_scale") = 1.0);
+  // GPU-only: ops.resgated_aggregate composes the CPU path from torch ops.
+  // An empty inv_deg is the plain sum.
+  m.def("resgated_fwd", &resgated_fwd_hip,
+        "residual gated aggregation over the CSR -> out; qv is [nodes, 2F] = "
+        "[Q | V]",
+        py::arg("indptr"), py::arg("indices"), py::arg("k"), py::arg("qv"),
+        py::arg("inv_deg"), py::arg("row_order"), py::arg("num_cols"));
+  m.def("resgated_bwd_dst", &resgated_bwd_dst_hip,
+        "residual gated aggregation backward over the CSR -> d_k",
+        py::arg("indptr"), py::arg("indices"), py::arg("g"), py::arg("k"),
+        py::arg("qv"), py::arg("inv_deg"), py::arg("row_order"),
+        py::arg("num_cols"));
+  m.def("resgated_bwd_src", &resgated_bwd_src_hip,
+        "residual gated aggregation backward over the CSC -> d_qv [nodes, 2F]",
+        py::arg("indptr"), py::arg("indices"), py::arg("g"), py::arg("k"),
+        py::arg("qv"), py::arg("inv_deg"), py::arg("row_order"),
+        py::arg("num_cols"));
   // GPU-only: ops.gated_residual composes the CPU path from torch ops
   m.def("gate_fwd", &gate_fwd_hip,
         "beta gate: sigmoid(<a, r> + <b, m>) mix of r and m -> (out, beta)",

@@ -361,6 +361,34 @@ torch::Tensor dot_bwd_src_hip(
     torch::Tensor row_order, int64_t num_cols, int64_t H, double scale,
     int64_t drop_key, int64_t drop_thr, double drop_scale);
 
+// Residual gated aggregation (csrc/hip/resgated.hip; docs/DESIGN.md,
+// "Residual gated aggregation"):
+//   s_uv[c] = sigmoid(k[v,c] + Q[u,c]), out[v] = inv_deg[v] * sum_u s_uv * V[u]
+// with Q = qv[:, :F] and V = qv[:, F:] the halves of one [nodes, 2F] record
+// (this layout is the op's contract), parallel edges counted. Every pass
+// recomputes the gate from the gathered rows; nothing of size nnz is
+// allocated. k/g/out/d_k are fp32 or bf16 [num_rows, F], F >= 1; qv/d_qv are
+// [nodes, 2F] of the same dtype; inv_deg is fp32 [num_rows], or undefined /
+// empty for the plain sum. -> out [num_rows, F]; rows without edges get 0.
+torch::Tensor resgated_fwd_hip(torch::Tensor indptr, torch::Tensor indices,
+                               torch::Tensor k, torch::Tensor qv,
+                               torch::Tensor inv_deg, torch::Tensor row_order,
+                               int64_t num_cols);
+// Destination-side backward over the CSR.
+// -> d_k [num_rows, F] = inv_deg[v] g[v] * sum_u s (1 - s) V[u].
+torch::Tensor resgated_bwd_dst_hip(torch::Tensor indptr, torch::Tensor indices,
+                                   torch::Tensor g, torch::Tensor k,
+                                   torch::Tensor qv, torch::Tensor inv_deg,
+                                   torch::Tensor row_order, int64_t num_cols);
+// Source-side backward; indptr/indices/row_order are the CSC with repeated
+// entries (rows = sources, num_cols = destinations). A prep pass first writes
+// the [k | inv_deg g] record [num_cols, 2F] that the entries gather.
+// -> d_qv [num_rows, 2F] = [d_Q | d_V].
+torch::Tensor resgated_bwd_src_hip(torch::Tensor indptr, torch::Tensor indices,
+                                   torch::Tensor g, torch::Tensor k,
+                                   torch::Tensor qv, torch::Tensor inv_deg,
+                                   torch::Tensor row_order, int64_t num_cols);
+
 // Fused SyncBatchNorm [+ReLU] (csrc/hip/batch_norm.hip). x/dy/y/dx are fp32
 // or bf16 contiguous [N, F] of one dtype, F >= 1, N >= 0; mean/std/w/b are
 // fp32 [F]; arithmetic and statistics in fp32. The column sums are added in

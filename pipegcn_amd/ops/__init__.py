@@ -1387,6 +1387,139 @@ def dot_aggregate_csr(csr: CSR, q: torch.Tensor, kv: torch.Tensor,
                                 num_heads, scale)[0]
 
 
+def _resgated_check(csr: CSR, k, qv, inv_deg) -> None:
+    """Shape guards shared by both residual-gated paths; raised before any
+    launch."""
+    if k.dim() != 2 or k.shape[1] < 1 or k.dtype not in (torch.float32,
+                                                         torch.bfloat16):
+        raise ValueError("resgated_aggregate: k must be a fp32 or bf16 "
+                         f"[num_dst, F] tensor, got {tuple(k.shape)} "
+                         f"{k.dtype}")
+    if qv.dim() != 2 or qv.shape[1] != 2 * k.shape[1]:
+        raise ValueError(
+            f"resgated_aggregate: qv must be [nodes, 2F] = [Q | V], got "
+            f"{tuple(qv.shape)} for k {tuple(k.shape)}")
+    if qv.shape[0] < csr.num_cols:
+        raise ValueError(
+            f"resgated_aggregate: qv has {qv.shape[0]} rows but the graph "
+            f"references {csr.num_cols} source nodes (an under-sized tensor "
+            "would be an out-of-bounds GPU gather)")
+    if k.shape[0] != csr.num_rows:
+        raise ValueError(
+            f"resgated_aggregate: k has {k.shape[0]} rows, the graph has "
+            f"{csr.num_rows} destination nodes")
+    if (qv.dtype != k.dtype or qv.device != k.device
+            or not (k.is_contiguous() and qv.is_contiguous())):
+        raise ValueError(
+            "resgated_aggregate: k and qv must be contiguous and of one "
+            f"dtype and device, got {k.dtype} / {qv.dtype}")
+    if inv_deg is not None and (
+            inv_deg.shape != (csr.num_rows,) or inv_deg.dtype != torch.float32
+            or inv_deg.device != k.device or not inv_deg.is_contiguous()):
+        raise ValueError(
+            "resgated_aggregate: inv_deg must be a contiguous fp32 "
+            f"[{csr.num_rows}] vector on k's device, got "
+            f"{tuple(inv_deg.shape)} {inv_deg.dtype}")
+
+
+def _resgated_aggregate_torch(csr: CSR, k, qv, inv_deg):
+    """Residual gated aggregation composed from torch ops under ordinary
+    autograd: the CPU test tier and rank-0 eval. [nnz, F] temporaries are
+    fine here; the GPU path never makes them."""
+    u, v = _edge_endpoints(csr)
+    feats = k.shape[1]
+    rec = qv.float().index_select(0, u)
+    s = torch.sigmoid(k.float().index_select(0, v) + rec[:, :feats])
+    out = torch.zeros(csr.num_rows, feats, device=k.device).index_add(
+        0, v, s * rec[:, feats:])
+    if inv_deg is not None:
+        out = out * inv_deg.unsqueeze(1)
+    return out.to(k.dtype)
+
+
+def _inv_deg_arg(inv_deg) -> torch.Tensor:
+    """inv_deg as the kernels take it: an empty tensor is the plain sum."""
+    return inv_deg if inv_deg is not None else torch.Tensor()
+
+
+def _resgated_forward_hip(csr: CSR, k, qv, inv_deg):
+    """One gather pass on the gfx950 kernel. Uses csr.row_order as given."""
+    return native().resgated_fwd(csr.indptr, csr.indices, k, qv,
+                                 _inv_deg_arg(inv_deg), _row_order(csr),
+                                 csr.num_cols)
+
+
+class _ResGatedAggregate(torch.autograd.Function):
+    """out[v] = inv_deg[v] * sum_u sigmoid(k[v] + Q[u]) * V[u] per channel,
+    with qv = [Q | V].
+
+    Saves k, qv and inv_deg only. The backward is two gather passes that
+    recompute the gate per edge: over the CSR for d_k, over the CSC for d_qv
+    (one [nodes, 2F] tensor, so the projection behind qv has one backward
+    GEMM).
+    """
+
+    @staticmethod
+    def forward(ctx, graph: HaloGraph, k, qv, inv_deg):
+        out = _resgated_forward_hip(graph.csr, k, qv, inv_deg)
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(k, qv, _inv_deg_arg(inv_deg))
+        ctx.graph = graph
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        k, qv, inv = ctx.saved_tensors
+        csr, csc = ctx.graph.csr, ctx.graph.csc
+        g = g.contiguous()
+        d_k = native().resgated_bwd_dst(
+            csr.indptr, csr.indices, g, k, qv, inv, _row_order(csr),
+            csr.num_cols)
+        d_qv = native().resgated_bwd_src(
+            csc.indptr, csc.indices, g, k, qv, inv, _row_order(csc),
+            csc.num_cols)
+        if d_qv.shape[0] < qv.shape[0]:  # rows the graph never references
+            d_qv = torch.cat((d_qv, d_qv.new_zeros(
+                qv.shape[0] - d_qv.shape[0], d_qv.shape[1])))
+        return None, d_k, d_qv, None
+
+
+def resgated_aggregate(graph: HaloGraph, k: torch.Tensor, qv: torch.Tensor,
+                       inv_deg: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Differentiable residual gated aggregation (the message function of
+    Bresson & Laurent's residual gated graph conv, PyG's ResGatedGraphConv)
+    over the halo graph.
+
+    k [num_in, F] is the destination-side term of the gate; qv [num_all, 2F]
+    holds, per local node, the source-side gate term Q = qv[:, :F] and the
+    value V = qv[:, F:] (this layout is the op's contract). Edge u -> v has
+    the per-channel weight sigmoid(k[v] + Q[u]), which is not normalised over
+    the neighbourhood. Returns out [num_in, F] = inv_deg[v] * sum_u s_uv *
+    V[u], repeated edges counted as often as they occur and rows without
+    edges 0. inv_deg is a contiguous fp32 [num_in] vector and gets no
+    gradient; None gives the plain sum (PyG's form). Nothing of size nnz is
+    allocated on the GPU path, forward or backward, and the result does not
+    depend on the row order (docs/DESIGN.md, "Residual gated aggregation").
+    k and qv must be contiguous and of one dtype, fp32 or bf16.
+    """
+    _resgated_check(graph.csr, k, qv, inv_deg)
+    if not k.is_cuda:
+        return _resgated_aggregate_torch(graph.csr, k, qv, inv_deg)
+    return _ResGatedAggregate.apply(graph, k, qv, inv_deg)
+
+
+def resgated_aggregate_csr(csr: CSR, k: torch.Tensor, qv: torch.Tensor,
+                           inv_deg: Optional[torch.Tensor] = None
+                           ) -> torch.Tensor:
+    """Forward-only residual gated aggregation over a plain CSR (full-graph
+    eval over FullGraph.csr)."""
+    _resgated_check(csr, k, qv, inv_deg)
+    with torch.no_grad():
+        if not k.is_cuda:
+            return _resgated_aggregate_torch(csr, k, qv, inv_deg)
+        return _resgated_forward_hip(csr, k, qv, inv_deg)
+
+
 def _gate_mix(r, m, a, b):
     """The gate from the folded vectors, as plain torch ops: the CPU path,
     and the formula the kernels are measured against."""

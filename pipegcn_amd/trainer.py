@@ -185,9 +185,10 @@ def create_model(layer_size, args):
     edge_drop = getattr(args, "edge_drop", 0.0)
     unmasked = ("pool", "pna", "softmax")
     if edge_drop > 0 and (aggregator in unmasked
-                          or args.model in ("gat", "gatv2", "transformer")):
-        # a masked max, multi or softmax gather is a later item; attention
-        # has --attn-drop
+                          or args.model in ("gat", "gatv2", "transformer",
+                                            "resgated")):
+        # a masked max, multi, softmax or gated gather is a later item;
+        # attention has --attn-drop
         what = (f"--aggregator {aggregator}" if aggregator in unmasked
                 else f"--model {args.model}")
         raise NotImplementedError(
@@ -235,6 +236,12 @@ def create_model(layer_size, args):
                            n_heads=getattr(args, "n_heads", 1),
                            attn_drop=getattr(args, "attn_drop", 0.0),
                            beta=beta_gate)
+    if args.model == "resgated":
+        from pipegcn_amd.models.resgated import ResGated
+
+        return ResGated(layer_size, F.relu, args.use_pp, norm=args.norm,
+                        dropout=args.dropout, n_linear=args.n_linear,
+                        train_size=args.n_train)
     raise NotImplementedError(f"unknown model {args.model}")
 
 

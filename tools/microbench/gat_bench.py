@@ -82,6 +82,15 @@ softmax aggregator.
 
     python tools/microbench/gat_bench.py --softmax --feats 602 [--rounds 7]
     python tools/microbench/gat_bench.py --epoch --softmax
+
+`--resgated` times the residual gated aggregation (csrc/hip/resgated.hip) at
+F = 64, 256 and 602 (`--feats` is not read): its forward and its backward
+over the CSR against the mean SpMM forward, its backward over the CSC against
+the transposed SpMM, on the same graph and width; min / median / max over the
+rounds, logical bytes/s, and exits. With `--epoch` it adds the ResGated model.
+
+    python tools/microbench/gat_bench.py --resgated [--rounds 7]
+    python tools/microbench/gat_bench.py --epoch --resgated
 """
 import argparse
 import json
@@ -130,6 +139,10 @@ ap.add_argument("--softmax", action="store_true",
                 help="time the softmax aggregation kernels against the mean "
                      "SpMM and its transpose; with --epoch: GraphSAGE with "
                      "the softmax aggregator")
+ap.add_argument("--resgated", action="store_true",
+                help="time the residual gated aggregation kernels at F = 64, "
+                     "256 and 602 against the mean SpMM and its transpose; "
+                     "with --epoch: the ResGated model")
 args = ap.parse_args()
 if args.pool and not args.epoch:
     ap.error("--pool times whole epochs: use it with --epoch")
@@ -381,12 +394,63 @@ def softmax_bench():
                       for k, b in model.items()})), flush=True)
 
 
+def resgated_bench():
+    nat, n_in, n_all = native(), rp.num_in, rp.num_all
+    for width in (64, 256, 602):
+        for dname in args.dtypes:
+            dtype = torch.bfloat16 if dname == "bf16" else torch.float32
+            es = 2 if dname == "bf16" else 4
+            gen = torch.Generator(device=dev).manual_seed(es)
+            k = torch.randn(n_in, width, device=dev, generator=gen).to(dtype)
+            qv = torch.randn(n_all, 2 * width, device=dev,
+                             generator=gen).to(dtype)
+            g = torch.randn(n_in, width, device=dev, generator=gen).to(dtype)
+            x = qv[:, :width].contiguous()  # the SpMM's rows, at the same F
+            csr_args = (k, qv, inv, ops._row_order(csr), csr.num_cols)
+            samples = bench_rounds({
+                "resgated_fwd": lambda: nat.resgated_fwd(
+                    csr.indptr, csr.indices, *csr_args),
+                "resgated_bwd_dst": lambda: nat.resgated_bwd_dst(
+                    csr.indptr, csr.indices, g, *csr_args),
+                "mean_fwd": lambda: ops.spmm(csr, x, inv),
+                "resgated_bwd_src": lambda: nat.resgated_bwd_src(
+                    csc.indptr, csc.indices, g, k, qv, inv,
+                    ops._row_order(csc), csc.num_cols),
+                "mean_bwd": lambda: ops.spmm(csc, g, None),
+            })
+            ms = {n: [round(t, 3)
+                      for t in (min(v), statistics.median(v), max(v))]
+                  for n, v in samples.items()}
+            # logical bytes: per edge the index and the gathered rows, per
+            # row what is read and written once
+            edge2 = nnz * (2 * es * width + 4)
+            model = {
+                "resgated_fwd": edge2 + 2 * n_in * width * es,
+                "resgated_bwd_dst": edge2 + 3 * n_in * width * es,
+                "mean_fwd": nnz * (es * width + 4) + n_in * width * es,
+                "resgated_bwd_src": edge2 + nnz * 4 + 4 * n_all * width * es,
+                "mean_bwd": nnz * (es * width + 4) + n_all * width * es,
+            }
+            print(json.dumps(dict(
+                mode="resgated", shape=args.shape, dtype=dname, F=width,
+                nnz=nnz, ms_min_median_max=ms,
+                fwd_ratio=round(ms["resgated_fwd"][1] / ms["mean_fwd"][1], 3),
+                bwd_dst_ratio=round(
+                    ms["resgated_bwd_dst"][1] / ms["mean_fwd"][1], 3),
+                bwd_src_ratio=round(
+                    ms["resgated_bwd_src"][1] / ms["mean_bwd"][1], 3),
+                model_gb={n: round(b / 1e9, 2) for n, b in model.items()},
+                tb_per_s={n: round(b / ms[n][1] / 1e9, 3)
+                          for n, b in model.items()})), flush=True)
+
+
 def epoch_bench():
     import torch.nn.functional as Fn
 
     from pipegcn_amd.models.gat import GAT
     from pipegcn_amd.models.gatv2 import GATv2
     from pipegcn_amd.models.gcn import GCN
+    from pipegcn_amd.models.resgated import ResGated
     from pipegcn_amd.models.sage import GraphSAGE
     from pipegcn_amd.models.transformer import Transformer
     from pipegcn_amd.parallel import context as ctx
@@ -420,6 +484,8 @@ def epoch_bench():
         if args.softmax:
             models.append(("graphsage-softmax", GraphSAGE,
                            dict(use_pp=False, aggregator="softmax"), deg))
+        if args.resgated:
+            models.append(("resgated", ResGated, {}, deg))
         if args.edge_drop > 0:
             models.append(("graphsage-edge-drop", GraphSAGE,
                            dict(use_pp=False, edge_drop=args.edge_drop), deg))
@@ -487,6 +553,10 @@ if args.pna:
 
 if args.softmax:
     softmax_bench()
+    sys.exit(0)
+
+if args.resgated:
+    resgated_bench()
     sys.exit(0)
 
 # (key, thr, scale) of the native entry points; (0, 0, 1.0) is no dropout
