@@ -6,7 +6,10 @@ spellings and defaults. `--norm none` is normalized to None by check_args
 `--model` takes the reference's graphsage and, as extensions, gcn, gat, gatv2,
 transformer and resgated (the residual gated graph conv; it reads neither
 `--n-heads` nor `--attn-drop` and refuses `--use-pp`, `--edge-drop`,
-`--beta-gate` and `--aggregator` other than mean).
+`--beta-gate` and `--aggregator` other than mean) and gcn2 (GCNII: a GCN
+layer, then square layers with an initial residual `--gcn2-alpha` and an
+identity mapping of strength `--gcn2-lambda`; it needs `--n-linear` >= 1 and
+has the same refusals).
 """
 import argparse
 
@@ -27,8 +30,18 @@ def create_parser(argv=None):
 
     parser.add_argument("--model", type=str, default="graphsage",
                         help="model for training: graphsage, gcn, gat, "
-                             "gatv2, transformer or resgated (the residual "
-                             "gated graph conv)")
+                             "gatv2, transformer, resgated (the residual "
+                             "gated graph conv) or gcn2 (GCNII)")
+    parser.add_argument("--gcn2-alpha", "--gcn2_alpha", type=float,
+                        default=0.1,
+                        help="GCNII's initial residual: the share of the "
+                             "first layer's output in every propagation "
+                             "(--model gcn2)")
+    parser.add_argument("--gcn2-lambda", "--gcn2_lambda", type=float,
+                        default=0.5,
+                        help="GCNII's identity mapping: layer l mixes its "
+                             "weight in with beta_l = log(lambda / l + 1) "
+                             "(--model gcn2)")
     parser.add_argument("--dropout", type=float, default=0.5,
                         help="dropout probability")
     parser.add_argument("--lr", type=float, default=1e-2,

@@ -478,6 +478,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("indptr"), py::arg("indices"), py::arg("g"), py::arg("k"),
         py::arg("qv"), py::arg("inv_deg"), py::arg("row_order"),
         py::arg("num_cols"));
+  // GPU-only: ops.gcn2_propagate composes the CPU path from torch ops. An
+  // empty d_src means h is scaled already; an empty dh0 skips the accumulate.
+  m.def("gcn2_fwd", &gcn2_fwd_hip,
+        "GCNII propagation over the CSR -> P = (1 - alpha) d_dst A (d_src h) "
+        "+ alpha h0",
+        py::arg("indptr"), py::arg("indices"), py::arg("h"), py::arg("h0"),
+        py::arg("d_dst"), py::arg("d_src"), py::arg("row_order"),
+        py::arg("num_cols"), py::arg("alpha"));
+  m.def("gcn2_bwd_prep", &gcn2_bwd_prep_hip,
+        "GCNII backward, one pass over dP -> gs = (1 - alpha) d_dst dP; "
+        "dh0 += alpha dP in place (fp32)",
+        py::arg("dp"), py::arg("d_dst"), py::arg("alpha"), py::arg("dh0"));
+  m.def("gcn2_bwd", &gcn2_bwd_hip,
+        "GCNII backward over the CSC -> dh = d_src * sum of gs",
+        py::arg("indptr"), py::arg("indices"), py::arg("gs"),
+        py::arg("d_src"), py::arg("row_order"), py::arg("num_cols"));
   // GPU-only: ops.gated_residual composes the CPU path from torch ops
   m.def("gate_fwd", &gate_fwd_hip,
         "beta gate: sigmoid(<a, r> + <b, m>) mix of r and m -> (out, beta)",

@@ -389,6 +389,30 @@ torch::Tensor resgated_bwd_src_hip(torch::Tensor indptr, torch::Tensor indices,
                                    torch::Tensor qv, torch::Tensor inv_deg,
                                    torch::Tensor row_order, int64_t num_cols);
 
+// GCNII propagation (csrc/hip/gcn2.hip; docs/DESIGN.md, "GCNII propagation"):
+//   P[v] = (1 - alpha) d_dst[v] sum_u d_src[u] h[u] + alpha h0[v]
+// over the CSR's edges u -> v, parallel edges counted; a row without edges
+// gives alpha h0[v]. h [>= num_cols, F] and h0 [>= num_rows, F] are fp32 or
+// bf16 of one dtype, F >= 1; d_dst fp32 [>= num_rows]; d_src fp32
+// [>= num_cols], or undefined / empty when the caller scaled h already; alpha
+// in [0, 1]. fp32 accumulation, one rounding. -> P [num_rows, F].
+torch::Tensor gcn2_fwd_hip(torch::Tensor indptr, torch::Tensor indices,
+                           torch::Tensor h, torch::Tensor h0,
+                           torch::Tensor d_dst, torch::Tensor d_src,
+                           torch::Tensor row_order, int64_t num_cols,
+                           double alpha);
+// One pass over dP [num_rows, F]: -> gs = (1 - alpha) d_dst[v] dP[v] in dP's
+// dtype, and, when dh0 (fp32 [>= num_rows, F]) is given, dh0[v] += alpha dP[v]
+// in place.
+torch::Tensor gcn2_bwd_prep_hip(torch::Tensor dp, torch::Tensor d_dst,
+                                double alpha, torch::Tensor dh0);
+// indptr/indices/row_order are the CSC with repeated entries (rows = sources
+// u, columns = destinations v < num_cols); gs [>= num_cols, F], d_src fp32
+// [>= rows]. -> dh [rows, F] = d_src[u] * sum_v gs[v].
+torch::Tensor gcn2_bwd_hip(torch::Tensor indptr, torch::Tensor indices,
+                           torch::Tensor gs, torch::Tensor d_src,
+                           torch::Tensor row_order, int64_t num_cols);
+
 // Fused SyncBatchNorm [+ReLU] (csrc/hip/batch_norm.hip). x/dy/y/dx are fp32
 // or bf16 contiguous [N, F] of one dtype, F >= 1, N >= 0; mean/std/w/b are
 // fp32 [F]; arithmetic and statistics in fp32. The column sums are added in

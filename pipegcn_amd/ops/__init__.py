@@ -1520,6 +1520,180 @@ def resgated_aggregate_csr(csr: CSR, k: torch.Tensor, qv: torch.Tensor,
         return _resgated_forward_hip(csr, k, qv, inv_deg)
 
 
+def _gcn2_check(csr: CSR, h, h0, d_dst, d_src, alpha) -> None:
+    """Guards shared by both GCNII paths; raised before any launch."""
+    if h.dim() != 2 or h.shape[1] < 1 or h.dtype not in (torch.float32,
+                                                         torch.bfloat16):
+        raise ValueError("gcn2_propagate: h must be a fp32 or bf16 "
+                         f"[nodes, F] tensor, got {tuple(h.shape)} {h.dtype}")
+    if h.shape[0] < csr.num_cols:
+        raise ValueError(
+            f"gcn2_propagate: h has {h.shape[0]} rows but the graph "
+            f"references {csr.num_cols} source nodes (an under-sized tensor "
+            "would be an out-of-bounds GPU gather)")
+    if h0.dim() != 2 or h0.shape[1] != h.shape[1] or h0.shape[0] < csr.num_rows:
+        raise ValueError(
+            f"gcn2_propagate: h0 is {tuple(h0.shape)}, the graph has "
+            f"{csr.num_rows} destination nodes of width {h.shape[1]}")
+    if (h0.dtype != h.dtype or h0.device != h.device
+            or not (h.is_contiguous() and h0.is_contiguous())):
+        raise ValueError(
+            "gcn2_propagate: h and h0 must be contiguous and of one dtype "
+            f"and device, got {h.dtype} / {h0.dtype}")
+    for name, d, n in (("d_dst", d_dst, csr.num_rows),
+                       ("d_src", d_src, csr.num_cols)):
+        if (d.dim() != 1 or d.shape[0] < n or d.dtype != torch.float32
+                or d.device != h.device or not d.is_contiguous()):
+            raise ValueError(
+                f"gcn2_propagate: {name} must be a contiguous fp32 vector "
+                f"with at least {n} entries on h's device, got "
+                f"{tuple(d.shape)} {d.dtype}")
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"gcn2_propagate: alpha={alpha} is outside [0, 1]")
+
+
+def _gcn2_propagate_torch(csr: CSR, h, h0, d_dst, d_src, alpha):
+    """GCNII propagation composed from torch index ops in the input dtype
+    under ordinary autograd: the CPU test tier and rank-0 eval. The [nnz, F]
+    temporary is fine here; the GPU path never makes it."""
+    u, v = _edge_endpoints(csr)
+    n = csr.num_rows
+    msg = h.index_select(0, u) * d_src[u].unsqueeze(1).to(h.dtype)
+    agg = torch.zeros(n, h.shape[1], dtype=h.dtype,
+                      device=h.device).index_add(0, v, msg)
+    scale = ((1.0 - alpha) * d_dst[:n]).unsqueeze(1).to(h.dtype)
+    return scale * agg + alpha * h0[:n]
+
+
+def _gcn2_forward_hip(csr: CSR, h, h0, d_dst, d_src, alpha, per_edge):
+    """One gather pass on the gfx950 kernel. per_edge: d_src[u] is loaded per
+    edge; else h is scaled by one streaming pass first. None takes
+    `_SpmmSym`'s cost rule: per edge unless nnz > numel."""
+    if per_edge is None:
+        per_edge = not csr.nnz > h.numel()
+    if per_edge:
+        src = d_src
+    else:
+        n = csr.num_cols
+        h, src = h[:n] * d_src[:n].unsqueeze(1).to(h.dtype), torch.Tensor()
+    return native().gcn2_fwd(csr.indptr, csr.indices, h, h0, d_dst, src,
+                             _row_order(csr), csr.num_cols, alpha)
+
+
+class _GCN2Propagate(torch.autograd.Function):
+    """P = (1 - alpha) D^{-1/2} A D^{-1/2} h + alpha h0 on the gfx950 kernels
+    (csrc/hip/gcn2.hip). Saves the degree vector only. Backward: one pass over
+    dP writes the row the transposed gather reads and adds alpha dP into the
+    running fp32 `dh0` buffer (h0 then gets no gradient from here: the
+    buffer's owner hands it on), one gather over the CSC gives dh."""
+
+    @staticmethod
+    def forward(ctx, graph: HaloGraph, h, h0, d, alpha, dh0, per_edge):
+        ctx.graph, ctx.alpha, ctx.dh0 = graph, alpha, dh0
+        ctx.rows = h.shape[0]
+        ctx.save_for_backward(d)
+        return _gcn2_forward_hip(graph.csr, h, h0, d, d, alpha, per_edge)
+
+    @staticmethod
+    def backward(ctx, dp):
+        d, = ctx.saved_tensors
+        csc, dh0 = ctx.graph.csc, ctx.dh0
+        dp = dp.contiguous()
+        fused = dh0 is not None and ctx.needs_input_grad[2]
+        gs = native().gcn2_bwd_prep(dp, d, ctx.alpha,
+                                    dh0 if fused else torch.Tensor())
+        dh = None
+        if ctx.needs_input_grad[1]:
+            dh = native().gcn2_bwd(csc.indptr, csc.indices, gs, d,
+                                   _row_order(csc), csc.num_cols)
+            if dh.shape[0] < ctx.rows:  # rows the graph never references
+                dh = torch.cat((dh, dh.new_zeros(ctx.rows - dh.shape[0],
+                                                 dh.shape[1])))
+        d_h0 = None
+        if ctx.needs_input_grad[2] and not fused:
+            d_h0 = ctx.alpha * dp
+        return None, dh, d_h0, None, None, None, None
+
+
+def gcn2_propagate(graph: HaloGraph, h: torch.Tensor, h0: torch.Tensor,
+                   deg_inv_sqrt: torch.Tensor, alpha: float,
+                   dh0: Optional[torch.Tensor] = None,
+                   per_edge: Optional[bool] = None) -> torch.Tensor:
+    """Differentiable GCNII propagation (Chen et al. 2020; the aggregation
+    and initial residual of PyG's GCN2Conv) over the halo graph:
+
+        P[v] = (1 - alpha) d[v] sum_{u in N(v)} d[u] h[u] + alpha h0[v]
+
+    h [num_all, F] and h0 [num_in, F] are contiguous and of one dtype, fp32
+    or bf16; deg_inv_sqrt = d is a contiguous fp32 [num_all] vector and gets
+    no gradient. Repeated edges count as often as they occur; a row without
+    edges gives alpha h0[v]. Returns P [num_in, F]; bf16 accumulates in fp32
+    and rounds once.
+
+    dh0 (GPU): a running fp32 [num_in, F] buffer. The backward then adds
+    alpha dP into it in the pass that prepares the transposed gather, and
+    returns no gradient for h0: the caller hands the buffer's sum to h0
+    once every layer that shares it has run. Without it h0's gradient is a
+    plain alpha * dP. per_edge picks the source-scale form (None: the cost
+    rule of the GCN layer). Nothing of size nnz is allocated on the GPU path
+    (docs/DESIGN.md, "GCNII propagation").
+    """
+    d = deg_inv_sqrt
+    _gcn2_check(graph.csr, h, h0, d, d, alpha)
+    if not h.is_cuda:
+        return _gcn2_propagate_torch(graph.csr, h, h0, d, d, alpha)
+    if dh0 is not None and (dh0.dtype != torch.float32
+                            or dh0.shape != (graph.num_in, h.shape[1])
+                            or not dh0.is_contiguous()
+                            or dh0.device != h.device):
+        raise ValueError("gcn2_propagate: dh0 must be a contiguous fp32 "
+                         f"[{graph.num_in}, {h.shape[1]}] buffer on h's "
+                         f"device, got {tuple(dh0.shape)} {dh0.dtype}")
+    return _GCN2Propagate.apply(graph, h, h0, d, alpha, dh0, per_edge)
+
+
+def gcn2_propagate_csr(csr: CSR, h: torch.Tensor, h0: torch.Tensor,
+                       d_dst: torch.Tensor, d_src: torch.Tensor,
+                       alpha: float,
+                       per_edge: Optional[bool] = None) -> torch.Tensor:
+    """Forward-only GCNII propagation over a plain CSR (full-graph eval over
+    FullGraph.csr), with the two sides' degree scales given apart."""
+    _gcn2_check(csr, h, h0, d_dst, d_src, alpha)
+    with torch.no_grad():
+        if not h.is_cuda:
+            return _gcn2_propagate_torch(csr, h, h0, d_dst, d_src, alpha)
+        return _gcn2_forward_hip(csr, h, h0, d_dst, d_src, alpha, per_edge)
+
+
+class _GCN2Mix(torch.autograd.Function):
+    """GCNII's identity mapping out = (1 - beta) P + beta P W^T as one addmm,
+    with dP = (1 - beta) dZ + beta dZ W and dW = beta dZ^T P one GEMM each: P
+    is saved once and no [N, F] temporary is made."""
+
+    @staticmethod
+    def forward(ctx, p, weight, beta):
+        ctx.beta = beta
+        ctx.save_for_backward(p, weight)
+        return torch.addmm(p, p, weight.t(), beta=1.0 - beta, alpha=beta)
+
+    @staticmethod
+    def backward(ctx, dz):
+        p, weight = ctx.saved_tensors
+        d_p = d_w = None
+        if ctx.needs_input_grad[0]:
+            d_p = torch.addmm(dz, dz, weight, beta=1.0 - ctx.beta,
+                              alpha=ctx.beta)
+        if ctx.needs_input_grad[1]:
+            d_w = torch.mm(dz.t(), p).mul_(ctx.beta)
+        return d_p, d_w, None
+
+
+def gcn2_mix(p: torch.Tensor, weight: torch.Tensor,
+             beta: float) -> torch.Tensor:
+    """(1 - beta) p + beta p @ weight.t() for a square weight [F, F]."""
+    return _GCN2Mix.apply(p, weight, beta)
+
+
 def _gate_mix(r, m, a, b):
     """The gate from the folded vectors, as plain torch ops: the CPU path,
     and the formula the kernels are measured against."""

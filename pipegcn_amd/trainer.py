@@ -186,7 +186,7 @@ def create_model(layer_size, args):
     unmasked = ("pool", "pna", "softmax")
     if edge_drop > 0 and (aggregator in unmasked
                           or args.model in ("gat", "gatv2", "transformer",
-                                            "resgated")):
+                                            "resgated", "gcn2")):
         # a masked max, multi, softmax or gated gather is a later item;
         # attention has --attn-drop
         what = (f"--aggregator {aggregator}" if aggregator in unmasked
@@ -242,6 +242,14 @@ def create_model(layer_size, args):
         return ResGated(layer_size, F.relu, args.use_pp, norm=args.norm,
                         dropout=args.dropout, n_linear=args.n_linear,
                         train_size=args.n_train)
+    if args.model == "gcn2":
+        from pipegcn_amd.models.gcn2 import GCN2
+
+        return GCN2(layer_size, F.relu, args.use_pp, norm=args.norm,
+                    dropout=args.dropout, n_linear=args.n_linear,
+                    train_size=args.n_train,
+                    alpha=getattr(args, "gcn2_alpha", 0.1),
+                    lam=getattr(args, "gcn2_lambda", 0.5))
     raise NotImplementedError(f"unknown model {args.model}")
 
 
@@ -298,7 +306,7 @@ def run(part: PartData, args, device: str = "cpu",
         feat = precompute(rp, args)
 
     in_deg = rp.ndata["in_degree"]
-    if args.model == "gcn":
+    if args.model in ("gcn", "gcn2"):
         # GCN's symmetric normalization needs halo-node degrees too
         in_deg = exchange_halo_values(rp, in_deg)
     labels_all = rp.ndata["label"]

@@ -36,6 +36,7 @@ ext = CUDAExtension(
         "pipegcn_amd/csrc/hip/gatv2.hip",
         "pipegcn_amd/csrc/hip/dot_attn.hip",
         "pipegcn_amd/csrc/hip/resgated.hip",
+        "pipegcn_amd/csrc/hip/gcn2.hip",
         "pipegcn_amd/csrc/hip/gate.hip",
         "pipegcn_amd/csrc/hip/batch_norm.hip",
     ],
